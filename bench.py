@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- 96x96 EPI patches/s, BASE fwd+bwd+Adam, global bs=512, on N MI355X of one node.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,12 @@ loss, backward, Adam) over one batch of synthetic patches already resident in HB
 batch is fixed at 512 (BASELINE.json), sharded 512/N per rank (strong scaling); one RCCL
 all-reduce of the flat gradient per step, bucketed and overlapped with backward.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (its roofline figures are
+read from HIP events inside the timed steps).  --full adds the measurements that take runs of
+their own: the exact-f32 and bf16x6 arithmetic legs, the UPR / DPP / shard64 / autograd-loop /
+ESE legs (the dpp / upr legs and ESE replicas under --gpus N) and the CPU baseline.
+--dump-outputs DIR writes what the last timed step left for its caller as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -195,6 +201,31 @@ def make_step(variant, B, patch, dev, seed):
     return step, stacks, gt, mask
 
 
+DUMP_BYTES = 60 << 20      # --dump-outputs: at most this many bytes of array data in all (below 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, step, loss):
+    """--dump-outputs: what the last timed step hands its caller -- the loss it returned and the model state it left (weights
+    after Adam, the gradient they were stepped with, the BatchNorm running statistics in state_dict order) -- as float32
+    DIR/<name>.npy.  An array that would take the total past DUMP_BYTES is replaced by a fixed, seeded sample of its elements
+    (none does at the shapes of this script: BASE weights and gradient are 18.4 MB each).  Returns {name: element count}."""
+    import numpy as np
+    bufs = [b.detach().reshape(-1) for _, b in step.model.named_buffers() if b.is_floating_point()]
+    arrays = {'loss': loss.detach().reshape(1), 'params': step.flat, 'grad': step.grad,
+              'bn_buffers': torch.cat(bufs) if bufs else torch.zeros(0)}
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = DUMP_BYTES, {}
+    for k, (name, t) in enumerate(arrays.items()):
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        room = left // (len(arrays) - k) // a.itemsize
+        if a.size > room:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, room, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes
+        written[name] = int(a.size)
+    return written
+
+
 def extra_leg(variant, B, patch, dev, steps, peak):
     """one more BASELINE.json config through the same train step, single GPU: value + whole-step TFLOP/s"""
     step, stacks, gt, mask = make_step(variant, B, patch, dev, seed=1)
@@ -323,13 +354,19 @@ def main():
     ap.add_argument('--variant', default='base', choices=['base', 'upr', 'dpp'])
     ap.add_argument('--global-batch', type=int, default=512)
     ap.add_argument('--patch', type=int, default=96)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-f32-leg', action='store_true', help='skip the extra exact-f32-MFMA measurement')
-    ap.add_argument('--no-extra-legs', action='store_true', help='skip the UPR / DPP / shard-64 / ESE measurements')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the legs below: exact-f32 / bf16x6 modes, UPR / DPP / shard-64 / '
+                         'autograd-loop / ESE (under --gpus N: dpp / upr legs and ESE replicas) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed (loss, weights after Adam, gradient, BatchNorm buffers) '
+                         'as DIR/<name>.npy, float32')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-f32-leg', action='store_true', help='with --full: skip the extra exact-f32-MFMA measurement')
+    ap.add_argument('--no-extra-legs', action='store_true', help='with --full: skip the UPR / DPP / shard-64 / ESE measurements')
     ap.add_argument('--ese-size', type=int, default=512, help='frame size of the ESE legs (BASELINE.json configs[4]: 512)')
     ap.add_argument('--rccl-self', action='store_true',
                     help='with --gpus 1: run the N > 1 code path of this script (process group on the nccl backend, distributed '
-                         'TrainStep, bucket waits, dpp / upr legs, ESE replica reductions) in a group of ONE rank -- a rehearsal of '
+                         'TrainStep, bucket waits; with --full the dpp / upr legs and ESE replica reductions) in a group of ONE rank -- a rehearsal of '
                          'every torch.distributed call under RCCL on a one-GPU box; no link traffic, not a scaling measurement')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='gloo: rehearsal of the N>1 path with every rank on whatever GPUs exist (one is enough)')
@@ -383,10 +420,12 @@ def main():
     it += args.steps
     prof, engine.PROFILE = engine.PROFILE, None
     peak_gib = torch.cuda.max_memory_allocated(dev) / 2.0 ** 30        # this rank's peak of live tensors over warm-up + timed steps
-    # further legs (N=1 only): the same step in the two arithmetic modes that carry no precision asterisk -- the exact-f32
+    if args.dump_outputs and rank == 0:          # before any further leg steps the same model
+        dump_outputs(args.dump_outputs, step, loss)
+    # further legs (--full, N=1 only): the same step in the two arithmetic modes that carry no precision asterisk -- the exact-f32
     # MFMA kernels (5 steps) and the exact 3 x bf16 split (3 steps) -- same tensors, same shapes
     mode_legs = {}
-    if not dist_on and not args.no_f32_leg:
+    if args.full and not dist_on and not args.no_f32_leg:
         for mode_name, nsteps in (('f32', 5), ('bf16x6', 3)):
             if engine.CONV_MODE == mode_name:
                 continue
@@ -428,7 +467,7 @@ def main():
     # through the 70-member Ensamble, no collective on the data path; reported as max-over-ranks seconds per scene
     ese_rep = None
     ddp_legs = {}
-    if dist_on and not args.no_extra_legs:
+    if args.full and dist_on and not args.no_extra_legs:
         passes_ = {'f16x3': 3, 'bf16x6': 6}.get(engine.CONV_MODE)
         peak_ = PEAK_BF16_MFMA_TFLOPS / passes_ if passes_ else PEAK_F32_MFMA_TFLOPS
         del step, stacks, gt, mask
@@ -490,6 +529,7 @@ def main():
         line['config']['build'] = _lib.build_info()
         line['config']['conv_cus'] = int(_lib.load().mmlf_conv_cus())
         line['config']['overlap_wgrad'] = int(engine.OVERLAP_WGRAD)
+        line['config']['full'] = bool(args.full)
         if nprof:      # the kernel furthest from its roof: the 70 -> 70 stream-layer convolutions, HBM-bound (70 FLOP/B < ridge)
             nsecs = sum(r[2].elapsed_time(r[3]) for r in nprof) * 1e-3
             nbytes = sum(r[4] for r in nprof)
@@ -561,7 +601,7 @@ def main():
             line['strict_precision'] = dict({k: v['value'] for k, v in mode_legs.items()}, unit='patches/s',
                                             note='bf16x6 = exact 3 x bf16 operand split, f32 = exact-f32 MFMA; `value` above is the '
                                                  'f16x3 mode (22 significant bits per operand, float32-level error measured)')
-        if not dist_on and not args.no_extra_legs and args.global_batch == 512 and args.patch == 96:
+        if args.full and not dist_on and not args.no_extra_legs and args.global_batch == 512 and args.patch == 96:
             # the other BASELINE.json configs, driver-timed in the same run (single GPU each)
             del step, stacks, gt, mask
             torch.cuda.empty_cache()
@@ -576,7 +616,7 @@ def main():
             line['autograd_loop']['note'] = ('model(h,v,i,d) -> mmlf_amd.loss module -> loss.backward() -> torch.optim.Adam.step() '
                                              '(mmlf/train/cli.py:243-258), head outputs materialised; vs_train_step = TrainStep ms / this ms')
             line['ese'] = ese_leg(dev, peak, size=args.ese_size)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args.variant, args.patch)
         print(json.dumps(line), flush=True)
     if dist_on:

@@ -189,7 +189,8 @@ def test_bench_two_ranks_gloo_rehearsal(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--global-batch', '8',
-           '--patch', '32', '--steps', '1', '--warmup', '1', '--backend', 'gloo', '--no-cpu-baseline', '--no-f32-leg', '--ese-size', '48']
+           '--patch', '32', '--steps', '1', '--warmup', '1', '--backend', 'gloo', '--full', '--no-cpu-baseline', '--no-f32-leg',
+           '--ese-size', '48']
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
@@ -224,7 +225,7 @@ def test_bench_rccl_self_rehearsal_prints_one_line():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--rccl-self', '--global-batch', '4', '--patch', '32',
-           '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--ese-size', '48']
+           '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--ese-size', '48']
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     out = [l for l in res.stdout.splitlines() if l.strip()]
