@@ -41,7 +41,7 @@ const char *mmlf_last_error(void);
 /* Bumped whenever an entry point's arguments or a layout they share changes.  mmlf_abi_version() returns the value the
  * library was BUILT with: a binding compares it with the header it was written against (mmlf_amd/_lib.py does, and reads
  * the number from this line) before making any other call. */
-#define MMLF_ABI_VERSION 8
+#define MMLF_ABI_VERSION 9
 int mmlf_abi_version(void);
 
 /* What the binary is: one line with the ABI version, the source revision it was built from and the value of every build
@@ -252,6 +252,41 @@ int mmlf_unpack_nchw(const float *grid, int cs, float *nchw, int C, int B, int H
 int mmlf_zero_slack(float *grid, int cs, int B, int H, int W, float *amax, void *stream);
 /* the same for up to four buffers of one (B, H, W) geometry in one launch (null grid pointers are skipped) */
 int mmlf_zero_slack4(float *const grid[4], const int cs[4], float *const amax[4], int B, int H, int W, void *stream);
+
+/* ---- 3x3 filters (--model_ksize 3, reference feed_forward.py:86-92,123,125: nn.Conv2d(k=3, padding=1) twice per block) ----
+ * Exact-f32 MFMA (v_mfma_f32_32x32x2_f32), independent of MMLF_CONV_MODE.  Both convolutions of a block are "same"
+ * convolutions: input and output have extent (H, W) at grid offset (1, 1); tap (dy, dx), dy, dx in {0, 1, 2}, reads
+ * position q + dy*P + dx and the result goes to q + P + 1.  The taps reach 2P + 2 positions past a tile, further than the
+ * 2x2 kernels: every grid buffer a 3x3 launch reads or writes holds mmlf_grid_alloc_positions_k3(B,H,W) positions and its
+ * slack is zeroed by mmlf_zero_slack_k3 / mmlf_zero_slack4_k3 (same arguments as mmlf_zero_slack / mmlf_zero_slack4). */
+int64_t mmlf_grid_alloc_positions_k3(int B, int H, int W);
+int mmlf_zero_slack_k3(float *grid, int cs, int B, int H, int W, float *amax, void *stream);
+int mmlf_zero_slack4_k3(float *const grid[4], const int cs[4], float *const amax[4], int B, int H, int W, void *stream);
+/* OIHW master filter (Cout,Cin,3,3) -> packed operand of mmlf_conv3x3 (mmlf_packed_filter3x3_floats(K, N) floats).
+ * dgrad = 0: K = Cin, N = Cout (forward).  dgrad = 1: K = Cout, N = Cin, taps rotated by 180 degrees (data gradient).
+ * variant: as mmlf_pack_filter (the H / I streams' transposed / transposed + flipped image). */
+int64_t mmlf_packed_filter3x3_floats(int K, int N);
+int mmlf_pack_filter3x3(const float *w_oihw, float *packed, int Cout, int Cin, int variant, int dgrad, void *stream);
+/* 9-tap correlation = nn.Conv2d(k=3, padding=1) forward or its data gradient:
+ *   out[q + P + 1][n] = valid(q) ? act(bias[n] + sum_t sum_k in[q + dy_t*P + dx_t][k] * Wp[t][k][n]) : 0
+ * valid(q): q < B*G, y < H, x < W.  relu / relu_ref / cs_ref / N_store as mmlf_conv2x2 (`out` may be a channel slice of a
+ * wider buffer: out + c_off with c_off + N_store <= cs_out).  `in` must be zero outside its extent. */
+int mmlf_conv3x3(const float *in, int cs_in, int K, const float *packed, const float *bias, int N,
+                 float *out, int cs_out, int N_store, int B, int H, int W, int relu, const float *relu_ref, int cs_ref,
+                 void *stream);
+/* weight + bias gradient:  gw[co][ci][sy][sx] (+)= sum_q in[q + dy*P + dx][ci] * g[q + P + 1][co] with (sy, sx) the master
+ * tap of packed tap (dy, dx) under `variant`, gb[co] (+)= sum_q g[q + P + 1][co] (gb nullable); g zero outside its extent.
+ * workspace: mmlf_wgrad3x3_workspace_floats(Cin, Cout, B, H, W) floats. */
+int64_t mmlf_wgrad3x3_workspace_floats(int Cin, int Cout, int B, int H, int W);
+int mmlf_conv3x3_wgrad(const float *in, int cs_in, int Cin, const float *g, int cs_g, int Cout, float *gw_oihw, float *gb,
+                       int variant, int accumulate, float *workspace, int B, int H, int W, void *stream);
+/* mmlf_fold_bn_eval for a (Cout, Cin, 3, 3) filter */
+int mmlf_fold_bn_eval3x3(const float *w_oihw, const float *bias, const float *scale, const float *shift,
+                         float *w_out, float *bias_out, int Cout, int Cin, void *stream);
+/* Bounds audit of one mmlf_conv3x3 / mmlf_conv3x3_wgrad launch: ends[0..4] in the order of MMLF_AUDIT_IN .. MMLF_AUDIT_REF
+ * (in, packed, bias, out, relu_ref) resp. MMLF_AUDIT_WG_IN .. MMLF_AUDIT_WG_WORKSPACE (in, g, gw, gb, workspace). */
+int mmlf_audit_conv3x3(int cs_in, int K, int N, int cs_out, int N_store, int cs_ref, int B, int H, int W, int64_t *ends);
+int mmlf_audit_wgrad3x3(int cs_in, int Cin, int cs_g, int Cout, int B, int H, int W, int64_t *ends);
 
 /* UPR head (feed_forward.py:292-302, laplacian :9-12): posterior[b,k,y,x] from output[:,0:2]. */
 int mmlf_head_upr(const float *output_nchw, const float *grid108, float *posterior, int steps,

@@ -77,6 +77,18 @@ SIGNATURES = {
     'mmlf_patch_gather': (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 12 + [_i, _i, _vp]),
     'mmlf_patch_contrast': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'mmlf_ensamble_reduce': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    # 3x3 filters (--model_ksize 3)
+    'mmlf_grid_alloc_positions_k3': (_i64, [_i, _i, _i]),
+    'mmlf_zero_slack_k3': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    'mmlf_zero_slack4_k3': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    'mmlf_packed_filter3x3_floats': (_i64, [_i, _i]),
+    'mmlf_pack_filter3x3': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'mmlf_conv3x3': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    'mmlf_wgrad3x3_workspace_floats': (_i64, [_i, _i, _i, _i, _i]),
+    'mmlf_conv3x3_wgrad': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
+    'mmlf_fold_bn_eval3x3': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    'mmlf_audit_conv3x3': (_i, [_i] * 9 + [_vp]),
+    'mmlf_audit_wgrad3x3': (_i, [_i] * 7 + [_vp]),
 }
 
 def _header_abi_version():

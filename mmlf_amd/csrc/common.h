@@ -110,6 +110,9 @@ static inline Grid make_grid(int B, int H, int W)
 
 // slack: taps reach P+1 past a tile; the split kernel's last DMA piece reads 64 positions more
 static inline long long grid_alloc_positions(const Grid &g) { return g.NQpad + g.P + 8 + 64; }
+// the same for the 3x3 ("same", pad 1) kernels: their taps reach 2P+2 past a tile (conv9tap_kernel reads positions up to
+// NQpad + 2P + 1, wgrad9tap_kernel up to NQpad + 2P + 1 as well)
+static inline long long grid_alloc_positions_k3(const Grid &g) { return g.NQpad + 2 * g.P + 8 + 64; }
 
 // ---- max |x| bookkeeping of the f16-split arithmetic ("amax array" of a grid tensor) ----
 // [k * MMLF_AMAX_SHARD_STRIDE], k < MMLF_AMAX_SHARDS: partial maxima of |x| over the whole tensor -- the tensor's maximum
@@ -160,6 +163,18 @@ __host__ __device__ static inline int master_tap(int t, int variant)
     if (variant == 0) return dy * 2 + dx;         // identity
     if (variant == 1) return dx * 2 + dy;         // transpose
     return dx * 2 + (1 - dy);                     // transpose, then flip along kernel-H
+}
+
+// the same for the 3x3 filters: packed tap t = dy*3 + dx (the launch reads q + dy*P + dx) -> sy*3+sx into the OIHW
+// (.,.,3,3) master.  The stream nets of the H / I stacks run on the transposed (and, for I, then W-flipped) image
+// (reference feed_forward.py:236-256); with centred taps the transposed image is served by the transposed filter and
+// the flipped one by sx = 2 - dy (tests/test_gpu_ksize3.py pins all three against nn.Conv2d on the transformed image).
+__host__ __device__ static inline int master_tap9(int t, int variant)
+{
+    const int dy = t / 3, dx = t - 3 * (t / 3);
+    if (variant == 0) return dy * 3 + dx;         // identity
+    if (variant == 1) return dx * 3 + dy;         // transpose
+    return dx * 3 + (2 - dy);                     // transpose, then flip along W of the transposed image
 }
 
 // Running maxima in device memory: fire-and-forget atomic max -- no read of the slot, nothing to wait for.

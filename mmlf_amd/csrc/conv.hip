@@ -1859,3 +1859,268 @@ extern "C" int mmlf_audit_conv_h2(int cs_in, int K, int N, int cs_out, int N_sto
     return 0;
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// 3x3 ("same", pad 1) convolution, exact-f32 MFMA: nn.Conv2d(k=3, padding=1) forward and data gradient
+// (reference feed_forward.py:123,125 with --model_ksize 3).  Nine taps at q + dy*P + dx, dy, dx in {0, 1, 2}; the
+// output goes to q + P + 1 (extent (H, W) at grid offset (1, 1)); the data gradient is the same correlation with the
+// taps rotated by 180 degrees and Cin / Cout swapped (pack_filter9_kernel, dgrad = 1).
+// ---------------------------------------------------------------------------------------------
+// OIHW (Cout, Cin, 3, 3) -> [chunk][tap(9)][kh(2)][NP][4] with k = 8*chunk + 4*kh + s
+__global__ void pack_filter9_kernel(const float *__restrict__ w, float *__restrict__ out, int Cout, int Cin,
+                                    int variant, int dgrad, int nchunk, int NP)
+{
+    const long long total = (long long)nchunk * 9 * 2 * NP * 4;
+    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * blockDim.x) {
+        int s = idx & 3;
+        long long r = idx >> 2;
+        int n = r % NP; r /= NP;
+        int kh = r & 1; r >>= 1;
+        int t = r % 9; r /= 9;
+        int c = (int)r;
+        int k = 8 * c + 4 * kh + s;
+        int ci, co, tsrc;
+        if (!dgrad) { ci = k; co = n; tsrc = t; }
+        else { co = k; ci = n; tsrc = 8 - t; }
+        float v = 0.f;
+        if (ci < Cin && co < Cout) v = w[((size_t)co * Cin + ci) * 9 + master_tap9(tsrc, variant)];
+        out[idx] = v;
+    }
+}
+
+// Tile of 256 positions (8 waves x 32) x NT*32 output channels; column block `cb` of `ncb` (blockIdx.x = tile*ncb + cb, so
+// the column blocks of a tile run side by side and share its activation window in L2).  Per 8-channel chunk:
+//   A (activations): [dy(3)][kh(2)][320] float4 -- rows dy of the window, positions Q0 + dy*P + 0..257
+//   B (weights)    : [tap(9)][kh(2)][NP] float4
+// LDS budget: 9 taps of B at 288 columns plus the 3-row window, double-buffered, would be 227 KB (160 KiB per CU), so the
+// columns per workgroup are bounded instead: NT <= 4 (<= 132 KiB double-buffered), 288 columns as three blocks of 96.
+// Single-buffering B would keep 288 columns per workgroup but expose the weight DMA once per chunk.
+template <int NT>
+__global__ __launch_bounds__(512) void conv9tap_kernel(ConvArgs a, int ncb, int np_total)
+{
+    constexpr int NP = NT * 32;
+    constexpr int A_STRIDE = 320;               // float4 slots per (dy, kh) array: 5 DMA pieces (258 used)
+    constexpr int A_F4 = 6 * A_STRIDE;
+    constexpr int B_F4 = 9 * 2 * NP;
+    constexpr int BUF_F4 = A_F4 + B_F4;
+    constexpr int N_A = 30;                     // DMA pieces for A per chunk
+    constexpr int N_PIECES = N_A + B_F4 / 64;   // + B pieces
+    constexpr int PER_WAVE = (N_PIECES + 7) / 8;
+    static_assert(B_F4 % 64 == 0 && PER_WAVE <= 9, "piece schedule: piece k of a wave is issued at tap k");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float4 *lds = reinterpret_cast<float4 *>(smem);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, kh = lane >> 5;
+    const int tile = blockIdx.x / ncb, cb = blockIdx.x - tile * ncb;
+    const long long Q0 = (long long)tile * MMLF_TILE;
+
+    f32x16 acc[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+
+    // per-lane DMA sources of this wave's pieces j = w, w+8, ...; chunk c adds c*step floats
+    const float *src[PER_WAVE];
+    int dst_f4[PER_WAVE];
+    int step[PER_WAVE];
+#pragma unroll
+    for (int k = 0; k < PER_WAVE; ++k) {
+        const int j = w + 8 * k;
+        if (j < N_A) {
+            const int arr = j / 5, blk = j - 5 * arr;           // arr = dy*2 + kh
+            int p = 64 * blk + lane;
+            p = p < 258 ? p : 257;                               // lanes past the window re-read its last position
+            src[k] = a.in + (size_t)(Q0 + (arr >> 1) * a.P + p) * a.cs_in + 4 * (arr & 1);
+            dst_f4[k] = arr * A_STRIDE + 64 * blk;
+            step[k] = 8;
+        } else {
+            const int b = (j < N_PIECES ? j : N_PIECES - 1) - N_A;
+            const int s = 64 * b + lane, tk = s / NP, n = s - tk * NP;   // tk = tap*2 + kh
+            src[k] = a.wp + ((size_t)tk * np_total + cb * NP + n) * 4;
+            dst_f4[k] = A_F4 + 64 * b;
+            step[k] = 18 * np_total * 4;
+        }
+    }
+    const unsigned lds_base = (unsigned)(size_t)(lds_void_t *)smem;
+
+#define CONV9_DMA_PIECE(c, buf, k)                                                                \
+    do {                                                                                          \
+        if ((k) < PER_WAVE && w + 8 * (k) < N_PIECES) {                                           \
+            const float *g_ = src[k] + (size_t)(c) * step[k];                                     \
+            const unsigned d_ = lds_base + (unsigned)(((buf) * BUF_F4 + dst_f4[k]) * 16);         \
+            unsigned keep_;                                                                       \
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"                \
+                         "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"                   \
+                         : "=&s"(keep_) : "v"(g_), "s"(d_) : "memory");                          \
+        }                                                                                         \
+    } while (0)
+#define CONV9_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+
+#pragma unroll
+    for (int k = 0; k < PER_WAVE; ++k) CONV9_DMA_PIECE(0, 0, k);
+    CONV9_DMA_WAIT();
+    __syncthreads();
+
+    for (int c = 0; c < a.nchunk; ++c) {
+        const int buf = c & 1;
+        const bool more = c + 1 < a.nchunk;
+        const float4 *base = lds + buf * BUF_F4;
+        const float4 *ap = base + kh * A_STRIDE + 32 * w + i;
+        const float4 *bp = base + A_F4 + kh * NP + i;
+        // the same software pipeline as conv4tap_kernel, over 9 taps: the fragment reads of tap t+1 are issued, then the
+        // 4*NT MFMAs of tap t run while they land; the DMA pieces of chunk c+1 are spread over the taps (piece k at tap k)
+        float4 a_cur = ap[0], b_cur[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) b_cur[nt] = bp[32 * nt];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            float4 a_nxt = a_cur, b_nxt[NT];
+            if (t < 8) {
+                const int dy = (t + 1) / 3, dx = (t + 1) - 3 * ((t + 1) / 3);
+                a_nxt = ap[dy * 2 * A_STRIDE + dx];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) b_nxt[nt] = bp[(t + 1) * 2 * NP + 32 * nt];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (more && w < 4) CONV9_DMA_PIECE(c + 1, buf ^ 1, t);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                if (nt == NT / 2) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (more && w >= 4) CONV9_DMA_PIECE(c + 1, buf ^ 1, t);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.x, b_cur[nt].x, acc[nt], 0, 0, 0);
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.y, b_cur[nt].y, acc[nt], 0, 0, 0);
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.z, b_cur[nt].z, acc[nt], 0, 0, 0);
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.w, b_cur[nt].w, acc[nt], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (t < 8) {
+                a_cur = a_nxt;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) b_cur[nt] = b_nxt[nt];
+            }
+        }
+        CONV9_DMA_WAIT();
+        __syncthreads();
+    }
+#undef CONV9_DMA_PIECE
+#undef CONV9_DMA_WAIT
+
+    // this column block's slice of the output channels: the shared epilogue on shifted pointers
+    ConvArgs e = a;
+    const int c0 = cb * NP;
+    e.out = a.out + c0;
+    e.out_bytes = a.out_bytes - 4ll * c0;
+    e.bias = a.bias ? a.bias + c0 : nullptr;
+    if (a.ref) { e.ref = a.ref + c0; e.ref_bytes = a.ref_bytes - 4ll * c0; }
+    e.n_store = a.n_store - c0;
+    e.n_true = a.n_true - c0;
+    conv_epilogue<NT>(e, acc, Q0, w, i, kh);
+}
+
+// 3x3 launch shape: NT 32-column tiles per workgroup, ncb column blocks
+static inline bool conv9_shape(int N, int *nt, int *ncb)
+{
+    const int n = pick_nt(N);
+    if (n < 0) return false;
+    *nt = n == 9 ? 3 : n;
+    *ncb = n == 9 ? 3 : 1;
+    return true;
+}
+
+extern "C" int64_t mmlf_packed_filter3x3_floats(int K, int N)
+{
+    const int nt = pick_nt(N);
+    if (nt < 0 || K <= 0) return -1;
+    return (int64_t)((K + 7) / 8) * 9 * 2 * (nt * 32) * 4;
+}
+
+extern "C" int mmlf_pack_filter3x3(const float *w, float *packed, int Cout, int Cin, int variant, int dgrad, void *stream)
+{
+    MMLF_CHECK_ARG(w && packed, "mmlf_pack_filter3x3: null pointer");
+    MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_pack_filter3x3: bad variant %d", variant);
+    MMLF_CHECK_ARG(Cout > 0 && Cin > 0, "mmlf_pack_filter3x3: bad channels %d x %d", Cout, Cin);
+    const int K = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;
+    const int nt = pick_nt(N);
+    MMLF_CHECK_ARG(nt > 0, "mmlf_pack_filter3x3: N=%d not supported (max 288)", N);
+    const int nchunk = (K + 7) / 8, NP = nt * 32;
+    const long long total = (long long)nchunk * 9 * 2 * NP * 4;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(pack_filter9_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin,
+                       variant, dgrad, nchunk, NP);
+    return mmlf_launch_status("mmlf_pack_filter3x3");
+}
+
+template <int NT>
+static int launch_conv9(const ConvArgs &a, long long ntiles, int ncb, int np_total, hipStream_t st)
+{
+    constexpr size_t lds = 2 * (6 * 320 + 9 * 2 * NT * 32) * sizeof(float4);
+    static_assert(lds <= 160 * 1024, "conv9tap_kernel: LDS per CU");
+    static PerDeviceOnce attr_once;
+    if (attr_once.run([] { return mmlf_allow_lds(reinterpret_cast<const void *>(conv9tap_kernel<NT>), lds, "mmlf_conv3x3"); }))
+        return 1;
+    hipLaunchKernelGGL(conv9tap_kernel<NT>, dim3((unsigned)(ntiles * ncb)), dim3(512), lds, st, a, ncb, np_total);
+    return mmlf_launch_status("mmlf_conv3x3");
+}
+
+extern "C" int mmlf_conv3x3(const float *in, int cs_in, int K, const float *packed, const float *bias, int N,
+                            float *out, int cs_out, int N_store, int B, int H, int W, int relu, const float *relu_ref,
+                            int cs_ref, void *stream)
+{
+    MMLF_CHECK_ARG(in && packed && out, "mmlf_conv3x3: null pointer");
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_conv3x3: bad shape B=%d H=%d W=%d", B, H, W);
+    MMLF_CHECK_ARG(cs_in > 0 && cs_in % 8 == 0, "mmlf_conv3x3: cs_in=%d must be a multiple of 8", cs_in);
+    MMLF_CHECK_ARG(K > 0 && (K + 7) / 8 * 8 == cs_in, "mmlf_conv3x3: K=%d does not match cs_in=%d", K, cs_in);
+    int nt, ncb;
+    MMLF_CHECK_ARG(conv9_shape(N, &nt, &ncb), "mmlf_conv3x3: N=%d not supported (max 288)", N);
+    MMLF_CHECK_ARG(N_store > 0 && N_store <= cs_out && N_store <= nt * ncb * 32,
+                   "mmlf_conv3x3: N_store=%d vs cs_out=%d NP=%d", N_store, cs_out, nt * ncb * 32);
+    MMLF_CHECK_ARG(!relu_ref || cs_ref >= N_store, "mmlf_conv3x3: cs_ref=%d < N_store", cs_ref);
+    const Grid g = make_grid(B, H, W);
+    MMLF_CHECK_ARG(g.NQpad + 2 * g.P + 64 < (1ll << 31), "mmlf_conv3x3: batch x image too large for 32-bit grid positions");
+    ConvArgs a = {};
+    a.in = in; a.wp = packed; a.bias = bias; a.out = out; a.ref = relu_ref;
+    a.NQ = g.NQ; a.cs_in = cs_in; a.nchunk = cs_in / 8; a.cs_out = cs_out; a.n_store = N_store; a.n_true = N;
+    a.out_shift = g.P + 1; a.vh = H; a.vw = W; a.P = g.P; a.G = g.G; a.relu = relu; a.cs_ref = cs_ref;
+    a.divP = make_magic((unsigned)g.P); a.divR = make_magic((unsigned)g.R); a.R = g.R;
+    const long long alloc = grid_alloc_positions_k3(g);
+    a.out_bytes = (alloc * cs_out - (cs_out - N_store)) * 4;
+    a.ref_bytes = relu_ref ? alloc * cs_ref * 4 : 0;
+    a.in_bytes = alloc * cs_in * 4;
+    const long long ntiles = g.NQpad / MMLF_TILE;
+    const int np_total = nt * ncb * 32;
+    hipStream_t st = (hipStream_t)stream;
+    switch (nt) {
+    case 1: return launch_conv9<1>(a, ntiles, ncb, np_total, st);
+    case 3: return launch_conv9<3>(a, ntiles, ncb, np_total, st);
+    default: return launch_conv9<4>(a, ntiles, ncb, np_total, st);
+    }
+}
+
+// Bounds audit of one mmlf_conv3x3 launch (ends[MMLF_AUDIT_IN .. MMLF_AUDIT_REF]): the last tile's window reads positions
+// NQpad - 256 + 2P + 0..257, B pieces read the whole packed filter, the epilogue writes q + P + 1 for q < NQpad.
+extern "C" int mmlf_audit_conv3x3(int cs_in, int K, int N, int cs_out, int N_store, int cs_ref, int B, int H, int W,
+                                  int64_t *ends /* [5] */)
+{
+    int nt, ncb;
+    MMLF_CHECK_ARG(conv9_shape(N, &nt, &ncb) && K > 0 && (K + 7) / 8 * 8 == cs_in && B > 0 && H > 0 && W > 0 && ends,
+                   "mmlf_audit_conv3x3: bad argument");
+    const Grid g = make_grid(B, H, W);
+    const long long last_in = (g.NQpad - MMLF_TILE) + 2 * g.P + 257;
+    const long long last_out = g.NQpad - 1 + g.P + 1;
+    ends[0] = (last_in + 1) * cs_in * 4;                                       // in
+    ends[1] = mmlf_packed_filter3x3_floats(cs_in, N) * 4;                      // packed
+    ends[2] = (int64_t)N * 4;                                                  // bias
+    ends[3] = (last_out * cs_out + N_store) * 4;                               // out
+    ends[4] = cs_ref ? (last_out * cs_ref + N_store) * 4 : 0;                  // relu_ref
+    return 0;
+}

@@ -22,6 +22,11 @@ extern "C" int64_t mmlf_grid_alloc_positions(int B, int H, int W)
     if (B <= 0 || H <= 0 || W <= 0) return -1;
     return grid_alloc_positions(make_grid(B, H, W));
 }
+extern "C" int64_t mmlf_grid_alloc_positions_k3(int B, int H, int W)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return -1;
+    return grid_alloc_positions_k3(make_grid(B, H, W));
+}
 
 // ---------------------------------------------------------------------------------------------
 // per-channel reductions over grid rows.  A block walks grid rows r = blockIdx.x, +gridDim.x, ...
@@ -1363,6 +1368,16 @@ extern "C" int mmlf_fold_bn_eval(const float *w_oihw, const float *bias, const f
     return mmlf_launch_status("mmlf_fold_bn_eval");
 }
 
+extern "C" int mmlf_fold_bn_eval3x3(const float *w_oihw, const float *bias, const float *scale, const float *shift,
+                                    float *w_out, float *bias_out, int Cout, int Cin, void *stream)
+{
+    MMLF_CHECK_ARG(w_oihw && scale && shift && w_out && bias_out && Cout > 0 && Cin > 0, "mmlf_fold_bn_eval3x3: bad argument");
+    const long long total = (long long)Cout * Cin * 9;
+    hipLaunchKernelGGL(fold_bn_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, w_oihw, bias, scale,
+                       shift, w_out, bias_out, Cout, Cin * 9);
+    return mmlf_launch_status("mmlf_fold_bn_eval3x3");
+}
+
 extern "C" int mmlf_bn_apply_relu(const float *z, int cs_z, int C, const float *scale, const float *shift, float *y,
                                   int cs_y, int c_off, int C_store, int B, int H, int W, float *amax_out,
                                   void *stream)
@@ -1452,16 +1467,27 @@ __global__ void zero_slack_kernel(float *__restrict__ buf, long long head, long 
     }
 }
 
-extern "C" int mmlf_zero_slack(float *grid, int cs, int B, int H, int W, float *amax, void *stream)
+// ksize: 2 = buffers of mmlf_grid_alloc_positions, 3 = of mmlf_grid_alloc_positions_k3
+static int zero_slack_impl(float *grid, int cs, int B, int H, int W, float *amax, int ksize, void *stream)
 {
     MMLF_CHECK_ARG(grid && cs > 0 && B > 0 && H > 0 && W > 0, "mmlf_zero_slack: bad argument");
     const Grid g = make_grid(B, H, W);
     const long long head = (long long)(g.P + 1) * cs, tail_off = g.NQ * cs;
-    const long long tail = (grid_alloc_positions(g) - g.NQ) * cs;
+    const long long tail = ((ksize == 3 ? grid_alloc_positions_k3(g) : grid_alloc_positions(g)) - g.NQ) * cs;
     const long long n_amax = amax ? amax_entries(g) : 0;
     hipLaunchKernelGGL(zero_slack_kernel, dim3(ew_blocks(head + tail + n_amax)), dim3(256), 0, (hipStream_t)stream, grid,
                        head, tail_off, tail, amax, n_amax);
     return mmlf_launch_status("mmlf_zero_slack");
+}
+
+extern "C" int mmlf_zero_slack(float *grid, int cs, int B, int H, int W, float *amax, void *stream)
+{
+    return zero_slack_impl(grid, cs, B, H, W, amax, 2, stream);
+}
+
+extern "C" int mmlf_zero_slack_k3(float *grid, int cs, int B, int H, int W, float *amax, void *stream)
+{
+    return zero_slack_impl(grid, cs, B, H, W, amax, 3, stream);
 }
 
 struct ZeroSlack4 { float *buf[4]; float *amax[4]; long long head[4], tail_off[4], tail[4], end[4]; long long n_amax; };
@@ -1475,7 +1501,8 @@ __global__ void zero_slack4_kernel(ZeroSlack4 z)
     }
 }
 
-extern "C" int mmlf_zero_slack4(float *const grid[4], const int cs[4], float *const amax[4], int B, int H, int W, void *stream)
+static int zero_slack4_impl(float *const grid[4], const int cs[4], float *const amax[4], int B, int H, int W, int ksize,
+                            void *stream)
 {
     MMLF_CHECK_ARG(grid && cs && amax && B > 0 && H > 0 && W > 0, "mmlf_zero_slack4: bad argument");
     const Grid g = make_grid(B, H, W);
@@ -1488,7 +1515,7 @@ extern "C" int mmlf_zero_slack4(float *const grid[4], const int cs[4], float *co
             MMLF_CHECK_ARG(cs[k] > 0, "mmlf_zero_slack4: cs[%d]=%d", k, cs[k]);
             z.head[k] = (long long)(g.P + 1) * cs[k];
             z.tail_off[k] = g.NQ * cs[k];
-            z.tail[k] = (grid_alloc_positions(g) - g.NQ) * cs[k];
+            z.tail[k] = ((ksize == 3 ? grid_alloc_positions_k3(g) : grid_alloc_positions(g)) - g.NQ) * cs[k];
             run += z.head[k] + z.tail[k] + (amax[k] ? amax_entries(g) : 0);
         }
         z.end[k] = run;
@@ -1497,6 +1524,17 @@ extern "C" int mmlf_zero_slack4(float *const grid[4], const int cs[4], float *co
     if (run == 0) return 0;
     hipLaunchKernelGGL(zero_slack4_kernel, dim3(ew_blocks(run)), dim3(256), 0, (hipStream_t)stream, z);
     return mmlf_launch_status("mmlf_zero_slack4");
+}
+
+extern "C" int mmlf_zero_slack4(float *const grid[4], const int cs[4], float *const amax[4], int B, int H, int W, void *stream)
+{
+    return zero_slack4_impl(grid, cs, amax, B, H, W, 2, stream);
+}
+
+extern "C" int mmlf_zero_slack4_k3(float *const grid[4], const int cs[4], float *const amax[4], int B, int H, int W,
+                                   void *stream)
+{
+    return zero_slack4_impl(grid, cs, amax, B, H, W, 3, stream);
 }
 
 extern "C" int mmlf_unpack_nchw(const float *grid, int cs, float *nchw, int C, int B, int H, int W, void *stream)

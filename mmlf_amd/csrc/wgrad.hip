@@ -728,10 +728,12 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
 // sum the position splits and scatter to the OIHW master gradient (+ bias gradient).  One thread per output element:
 // at 64 patches per GPU this launch is latency-bound and wants every CU full of waves -- a float4-per-thread form with a
 // quarter of the threads ran 2.5x longer (130 vs 50 us at 280 -> 280, measured in the step).
+// NTAP = 4 (2x2 filters, partials [nsplit][4][CIP][NP]) or 9 (3x3 filters, wgrad9tap_kernel's [nsplit][9][CIP][NP]).
+template <int NTAP>
 __global__ void wgrad_reduce_kernel(const float *__restrict__ part, float *__restrict__ gw, float *__restrict__ gb,
                                      int Cin, int Cout, int CIP, int NP, int nsplit, int variant, int accumulate)
 {
-    const int total = 4 * (Cin + 1) * Cout;
+    const int total = NTAP * (Cin + 1) * Cout;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int co = idx % Cout;
@@ -740,7 +742,7 @@ __global__ void wgrad_reduce_kernel(const float *__restrict__ part, float *__res
     const int t = r / (Cin + 1);
     if (ci == Cin && (t != 0 || gb == nullptr)) return;
     const float *pp = part + ((size_t)t * CIP + ci) * NP + co;
-    const size_t stride = (size_t)4 * CIP * NP;
+    const size_t stride = (size_t)NTAP * CIP * NP;
     constexpr int U = 16;
     double acc[U];
 #pragma unroll
@@ -762,7 +764,7 @@ __global__ void wgrad_reduce_kernel(const float *__restrict__ part, float *__res
     if (ci == Cin) {
         gb[co] = accumulate ? gb[co] + (float)s : (float)s;
     } else {
-        const size_t o = ((size_t)co * Cin + ci) * 4 + master_tap(t, variant);
+        const size_t o = ((size_t)co * Cin + ci) * NTAP + (NTAP == 4 ? master_tap(t, variant) : master_tap9(t, variant));
         gw[o] = accumulate ? gw[o] + (float)s : (float)s;
     }
 }
@@ -981,7 +983,7 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
         rc = planes == 3 ? launch_wgrad_split<3>(c, a, st) : launch_wgrad_split<2>(c, a, st);
         if (rc) return rc;
         const int total = 4 * (Cin + 1) * Cout;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, workspace, gw, gb, Cin,
+        hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((total + 255) / 256), dim3(256), 0, st, workspace, gw, gb, Cin,
                            Cout, a.nslice * 16 * c.mb, 16 * c.nb, a.nsplit, variant, accumulate);
         return mmlf_launch_status("mmlf_conv2x2_wgrad(reduce)");
     }
@@ -993,7 +995,7 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
     }
     if (rc) return rc;
     const int total = 4 * (Cin + 1) * Cout;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, workspace, gw, gb, Cin,
+    hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((total + 255) / 256), dim3(256), 0, st, workspace, gw, gb, Cin,
                        Cout, a.nslice * 32, nt * 32, a.nsplit, variant, accumulate);
     return mmlf_launch_status("mmlf_conv2x2_wgrad(reduce)");
 }
@@ -1124,5 +1126,199 @@ extern "C" int mmlf_audit_wgrad_h2(int cs_in, int Cin, int cs_g, int Cout, int g
                : wgrad_partial_floats(Cin, Cout) + 2 * nchunks + 2) * 4;        // ... then the per-chunk and the two tensor scales
     ends[5] = (MMLF_AMAX_HEAD + amax_rows(g)) * 4;                            // in_amax (the scale kernel clamps rows to amax_rows - 1)
     ends[6] = ends[5];                                                        // g_amax
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// weight + bias gradient of the 3x3 ("same", pad 1) convolution, exact-f32 MFMA:
+//   gw[co][ci][tap] (+)= sum_q in[q + dy*P + dx][ci] * g[q + P + 1][co],  gb[co] (+)= sum_q g[q + P + 1][co]
+// The decomposition of wgrad4tap_kernel with one tap ROW per workgroup: 192 threads = 3 waves, wave = dx; block =
+// (32-channel ci slice, dy, position split), so that nine accumulator sets of up to 9 x 16 registers never share a
+// workgroup.  The gradient tile is staged once per (slice, dy) block; the three dy blocks of a slice read it from L2.
+// ---------------------------------------------------------------------------------------------
+template <int NT>
+__global__ __launch_bounds__(192, 2) void wgrad9tap_kernel(WgradArgs a)
+{
+    constexpr int NP = NT * 32;
+    constexpr int ROWS = WG_KQ + 2;        // positions of one tap row: the chunk's 32 and the two dx behind them
+    constexpr int A_FL = ROWS * 32;        // floats
+    constexpr int A_F4 = A_FL / 4;         // 272
+    constexpr int NA = (A_F4 + 191) / 192;
+    constexpr int G_F4 = WG_KQ * NP / 4;
+    constexpr int NG = (G_F4 + 191) / 192;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float *As = reinterpret_cast<float *>(smem);
+    float *Gs = As + A_FL;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, dx = tid >> 6;
+    const int i = lane & 31, kh = lane >> 5;
+    int sd, split;
+    if (!wgrad_block_map(a, sd, split)) return;
+    const int slice = sd / 3, dy = sd - 3 * slice;
+    const int ci0 = slice * 32;
+    int c_begin = split * a.chunks_per_split;
+    int c_end = c_begin + a.chunks_per_split;
+    if (c_end > a.nchunks) c_end = a.nchunks;
+
+    f32x16 acc[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+
+    float4 ra[NA], rg[NG];
+    auto gload = [&](int c) {
+        const long long Qc = (long long)c * WG_KQ + (long long)dy * a.P;
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const int idx = tid + 192 * j;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (idx < A_F4) {
+                const int row = idx >> 3, ch = ci0 + 4 * (idx & 7);
+                if (ch < a.cs_in) v = *reinterpret_cast<const float4 *>(a.in + (size_t)(Qc + row) * a.cs_in + ch);
+            }
+            ra[j] = v;
+        }
+        const long long Qg = (long long)c * WG_KQ + a.g_shift;
+#pragma unroll
+        for (int j = 0; j < NG; ++j) {
+            const int idx = tid + 192 * j;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (idx < G_F4) {
+                const int row = idx / (NP / 4), f = idx - row * (NP / 4);
+                if (4 * f < a.cs_g) v = *reinterpret_cast<const float4 *>(a.g + (size_t)(Qg + row) * a.cs_g + 4 * f);
+            }
+            rg[j] = v;
+        }
+    };
+    auto lstore = [&]() {
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const int idx = tid + 192 * j;
+            if (idx < A_F4) {
+                float4 v = ra[j];          // ones row (bias gradient) patched at store time
+                const int ch = ci0 + 4 * (idx & 7);
+                if (ch == a.cin) v.x = 1.f;
+                if (ch + 1 == a.cin) v.y = 1.f;
+                if (ch + 2 == a.cin) v.z = 1.f;
+                if (ch + 3 == a.cin) v.w = 1.f;
+                reinterpret_cast<float4 *>(As)[idx] = v;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NG; ++j) {
+            const int idx = tid + 192 * j;
+            if (idx < G_F4) reinterpret_cast<float4 *>(Gs)[idx] = rg[j];
+        }
+    };
+
+    if (c_begin < c_end) {
+        gload(c_begin);
+        for (int c = c_begin; c < c_end; ++c) {
+            lstore();
+            __syncthreads();
+            if (c + 1 < c_end) gload(c + 1);
+            const float *ap = As + (dx + kh) * 32 + i;
+            const float *gp = Gs + kh * NP + i;
+#pragma unroll
+            for (int s = 0; s < WG_KQ / 2; ++s) {
+                const float av = ap[2 * s * 32];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const float bv = gp[2 * s * NP + 32 * nt];
+                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[nt], 0, 0, 0);
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int CIP = a.nslice / 3 * 32;
+    float *pp = a.part + ((size_t)(split * 9 + 3 * dy + dx) * CIP + ci0) * NP;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
+            pp[(size_t)row * NP + 32 * nt + i] = acc[nt][r];
+        }
+}
+
+// launch layout of the 3x3 weight gradient: 3 * (ci slices) x position splits
+struct Wgrad9Cfg { int nt, nslice, nsplit; };
+static inline bool wgrad9_cfg(int Cin, int Cout, Wgrad9Cfg *c)
+{
+    c->nt = pick_nt(Cout);
+    if (c->nt < 0 || Cin <= 0) return false;
+    c->nslice = 3 * ((Cin + 1 + 31) / 32);      // +1: the ones row that yields the bias gradient
+    c->nsplit = wgrad_nsplit(c->nslice);
+    return true;
+}
+
+extern "C" int64_t mmlf_wgrad3x3_workspace_floats(int Cin, int Cout, int B, int H, int W)
+{
+    Wgrad9Cfg c;
+    if (!wgrad9_cfg(Cin, Cout, &c) || B <= 0 || H <= 0 || W <= 0) return -1;
+    return (int64_t)c.nsplit * 9 * (c.nslice / 3 * 32) * (c.nt * 32);
+}
+
+template <int NT>
+static int launch_wgrad9(const WgradArgs &a, hipStream_t st)
+{
+    constexpr size_t lds = ((WG_KQ + 2) * 32 + WG_KQ * NT * 32) * sizeof(float);
+    hipLaunchKernelGGL(wgrad9tap_kernel<NT>, dim3(wgrad_grid_blocks(a.nslice, a.nsplit)), dim3(192), lds, st, a);
+    return mmlf_launch_status("mmlf_conv3x3_wgrad");
+}
+
+extern "C" int mmlf_conv3x3_wgrad(const float *in, int cs_in, int Cin, const float *g, int cs_g, int Cout, float *gw_oihw,
+                                  float *gb, int variant, int accumulate, float *workspace, int B, int H, int W, void *stream)
+{
+    MMLF_CHECK_ARG(in && g && gw_oihw && workspace, "mmlf_conv3x3_wgrad: null pointer");
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_conv3x3_wgrad: bad shape B=%d H=%d W=%d", B, H, W);
+    MMLF_CHECK_ARG(cs_in % 4 == 0 && cs_g % 4 == 0, "mmlf_conv3x3_wgrad: strides must be multiples of 4");
+    MMLF_CHECK_ARG(Cin > 0 && Cin <= cs_in && Cout > 0 && Cout <= cs_g, "mmlf_conv3x3_wgrad: channels vs strides");
+    MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_conv3x3_wgrad: bad variant");
+    Wgrad9Cfg c;
+    MMLF_CHECK_ARG(wgrad9_cfg(Cin, Cout, &c), "mmlf_conv3x3_wgrad: Cout=%d not supported", Cout);
+    const Grid gr = make_grid(B, H, W);
+    MMLF_CHECK_ARG(gr.NQpad + 2 * gr.P + 64 < (1ll << 31), "mmlf_conv3x3_wgrad: batch x image too large");
+    WgradArgs a = {};
+    a.in = in; a.g = g; a.part = workspace; a.NQpad = gr.NQpad;
+    a.cs_in = cs_in; a.cin = Cin; a.cs_g = cs_g; a.g_shift = gr.P + 1; a.P = gr.P;
+    a.in_bytes = grid_alloc_positions_k3(gr) * cs_in * 4; a.g_bytes = grid_alloc_positions_k3(gr) * cs_g * 4;
+    a.part_floats = mmlf_wgrad3x3_workspace_floats(Cin, Cout, B, H, W);
+    a.nslice = c.nslice;
+    a.nsplit = c.nsplit;
+    a.nchunks = (int)(gr.NQpad / WG_KQ);
+    a.chunks_per_split = (a.nchunks + a.nsplit - 1) / a.nsplit;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    switch (c.nt) {
+    case 1: rc = launch_wgrad9<1>(a, st); break;
+    case 3: rc = launch_wgrad9<3>(a, st); break;
+    case 4: rc = launch_wgrad9<4>(a, st); break;
+    default: rc = launch_wgrad9<9>(a, st); break;
+    }
+    if (rc) return rc;
+    const int total = 9 * (Cin + 1) * Cout;
+    hipLaunchKernelGGL(wgrad_reduce_kernel<9>, dim3((total + 255) / 256), dim3(256), 0, st, workspace, gw_oihw, gb, Cin,
+                       Cout, c.nslice / 3 * 32, c.nt * 32, c.nsplit, variant, accumulate);
+    return mmlf_launch_status("mmlf_conv3x3_wgrad(reduce)");
+}
+
+// Bounds audit of one mmlf_conv3x3_wgrad launch (ends[MMLF_AUDIT_WG_IN .. MMLF_AUDIT_WG_WORKSPACE]): chunk c stages
+// in[32 c + dy P .. + 33] and g[32 c + P + 1 .. + 31], c < NQpad / 32.
+extern "C" int mmlf_audit_wgrad3x3(int cs_in, int Cin, int cs_g, int Cout, int B, int H, int W, int64_t *ends /* [5] */)
+{
+    Wgrad9Cfg c;
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0 && ends && wgrad9_cfg(Cin, Cout, &c), "mmlf_audit_wgrad3x3: bad argument");
+    const Grid g = make_grid(B, H, W);
+    const long long last_c = g.NQpad - WG_KQ;
+    const int slice_end = c.nslice / 3 * 32;                                  // channels the last slice stages (< cs_in only)
+    ends[0] = ((last_c + 2 * g.P + WG_KQ + 1) * cs_in + (slice_end < cs_in ? slice_end : cs_in)) * 4;   // in
+    ends[1] = ((last_c + g.P + 1 + WG_KQ - 1) * cs_g + (c.nt * 32 < cs_g ? c.nt * 32 : cs_g)) * 4;     // g
+    ends[2] = (int64_t)Cout * Cin * 9 * 4;                                    // gw (OIHW)
+    ends[3] = (int64_t)Cout * 4;                                              // gb
+    ends[4] = mmlf_wgrad3x3_workspace_floats(Cin, Cout, B, H, W) * 4;         // workspace
     return 0;
 }

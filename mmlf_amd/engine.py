@@ -24,13 +24,18 @@ def cs_of(c):
 
 
 class Geometry:
-    def __init__(self, B, H, W):
+    """ksize 3: buffers sized and zeroed for the 3x3 kernels, whose taps reach 2P + 2 positions past a tile
+    (mmlf_grid_alloc_positions_k3; the 2x2 allocation does not grow)"""
+
+    def __init__(self, B, H, W, ksize=2):
         self.B, self.H, self.W = B, H, W
+        self.ksize = ksize
         # pitch W + 2, H + 2 rows (the library's build options MMLF_GRID_PAD_W / _H: csrc/common.h has the measured alternatives)
         self.P, self.R = W + int(_lib.load().mmlf_grid_pad_w()), H + int(_lib.load().mmlf_grid_pad_h())
         self.G = self.P * self.R
         self.NQ = B * self.G
-        self.alloc = int(_lib.load().mmlf_grid_alloc_positions(B, H, W))
+        self.alloc = int(_lib.load().mmlf_grid_alloc_positions_k3(B, H, W) if ksize == 3
+                         else _lib.load().mmlf_grid_alloc_positions(B, H, W))
         self.amax_n = int(_lib.load().mmlf_amax_entries(B, H, W))
         self.amax_head = int(_lib.load().mmlf_amax_head())             # tensor-maximum shards, then one entry per grid row
         self.amax_stride = int(_lib.load().mmlf_amax_shard_stride())
@@ -44,7 +49,8 @@ class Geometry:
         f16-split kernels derive their power-of-two operand scales from them (include/mmlf_hip.h)."""
         t = torch.empty(self.alloc * cs, dtype=torch.float32, device=device)
         t.absmax = torch.empty(self.amax_n, dtype=torch.float32, device=device)
-        call('mmlf_zero_slack', ptr(t), cs, self.B, self.H, self.W, ptr(t.absmax), _lib.stream_ptr())
+        call('mmlf_zero_slack_k3' if self.ksize == 3 else 'mmlf_zero_slack', ptr(t), cs, self.B, self.H, self.W, ptr(t.absmax),
+             _lib.stream_ptr())
         return t
 
     def bufs(self, css, device):
@@ -62,7 +68,8 @@ class Geometry:
         grid = (ctypes.c_void_p * 4)(*([ptr(t) for t in ts] + [None] * (4 - n)))
         amax = (ctypes.c_void_p * 4)(*([ptr(t.absmax) for t in ts] + [None] * (4 - n)))
         csa = (ctypes.c_int * 4)(*(list(css) + [0] * (4 - n)))
-        call('mmlf_zero_slack4', grid, csa, amax, self.B, self.H, self.W, _lib.stream_ptr())
+        call('mmlf_zero_slack4_k3' if self.ksize == 3 else 'mmlf_zero_slack4', grid, csa, amax, self.B, self.H, self.W,
+             _lib.stream_ptr())
         return ts
 
     def relu_mask(self, device):
@@ -185,7 +192,8 @@ class _Workspace:
         return t
 
     def wgrad_ws(self, geo, cin, cout, side=False):
-        n = int(_lib.load().mmlf_wgrad_workspace_floats(cin, cout, geo.B, geo.H, geo.W))
+        query = _lib.load().mmlf_wgrad3x3_workspace_floats if geo.ksize == 3 else _lib.load().mmlf_wgrad_workspace_floats
+        n = int(query(cin, cout, geo.B, geo.H, geo.W))
         if n < 0:
             raise RuntimeError(f'wgrad: unsupported channels {cin}->{cout}')
         name = 'wgrad_side' if side else 'wgrad'
@@ -382,6 +390,56 @@ def conv(geo, x, cs_in, K, packed, bias, N, out, cs_out, out_shift, vh, vw, relu
         PROFILE.append(('conv' if K >= 256 else 'conv70', 2.0 * geo.B * vh * vw * N * 4 * K, e0, e1, nbytes))
 
 
+# ---------------------------------------------------------------------------------------------- 3x3 filters (--model_ksize 3)
+# Exact-f32 MFMA kernels whatever MMLF_CONV_MODE says (include/mmlf_hip.h): both convolutions of a block are "same"
+# convolutions, input and output at grid offset (1, 1) with extent (H, W).
+
+def pack_filter3(w, variant, dgrad):
+    cout, cin = w.shape[0], w.shape[1]
+    K, N = (cout, cin) if dgrad else (cin, cout)
+    n = int(_lib.load().mmlf_packed_filter3x3_floats(cs_of(K), N))
+    if n < 0:
+        raise RuntimeError(f'pack_filter3: unsupported channels K={K} N={N}')
+    out = torch.empty(n, dtype=torch.float32, device=w.device)
+    call('mmlf_pack_filter3x3', ptr(w), ptr(out), cout, cin, variant, int(dgrad), _lib.stream_ptr())
+    return out
+
+
+def conv3(geo, x, cs_in, K, packed, bias, N, out, cs_out, relu, ref=None, cs_ref=0, n_store=None, out_off=0):
+    """3x3 forward (or, on a dgrad-packed filter, data gradient): out[q + P + 1] from x[q + dy*P + dx]"""
+    n_store = cs_out if n_store is None else n_store
+    if CHECK_EXTENTS:
+        import ctypes
+        e = (ctypes.c_int64 * 5)()
+        call('mmlf_audit_conv3x3', cs_in, K, N, cs_out, n_store, cs_ref if ref is not None else 0, geo.B, geo.H, geo.W, e)
+        _check_extents(f'conv3x3 {K}->{N} B={geo.B} {geo.H}x{geo.W}', e,
+                       {'in': (e[0], x, 0), 'packed': (e[1], packed, 0), 'bias': (e[2], bias, 0), 'out': (e[3], out, out_off),
+                        'ref': (e[4], ref, 0)})
+    prof = PROFILE is not None and K >= 256 and N >= 256
+    if prof:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    call('mmlf_conv3x3', ptr(x), cs_in, K, ptr(packed), ptr(bias), N, ptr(out) + 4 * out_off, cs_out, n_store,
+         geo.B, geo.H, geo.W, int(relu), ptr(ref), cs_ref, _lib.stream_ptr())
+    if prof:
+        e1.record()
+        nbytes = 4.0 * geo.B * geo.H * geo.W * (K + N)
+        PROFILE.append(('conv3x3', 2.0 * geo.B * geo.H * geo.W * N * 9 * K, e0, e1, nbytes))
+
+
+def wgrad3(geo, x, cs_in, cin, g, cs_g, cout, gw, gb, variant, workspace):
+    """3x3 weight + bias gradient, accumulated into gw / gb"""
+    if CHECK_EXTENTS:
+        import ctypes
+        e = (ctypes.c_int64 * 5)()
+        call('mmlf_audit_wgrad3x3', cs_in, cin, cs_g, cout, geo.B, geo.H, geo.W, e)
+        _check_extents(f'wgrad3x3 {cin}->{cout} B={geo.B} {geo.H}x{geo.W}', e,
+                       {'in': (e[0], x, 0), 'g': (e[1], g, 0), 'gw': (e[2], gw, 0), 'gb': (e[3], gb, 0),
+                        'workspace': (e[4], workspace, 0)})
+    call('mmlf_conv3x3_wgrad', ptr(x), cs_in, cin, ptr(g), cs_g, cout, ptr(gw), ptr(gb), variant, 1, ptr(workspace),
+         geo.B, geo.H, geo.W, _lib.stream_ptr())
+
+
 class BlockSpec:
     def __init__(self, prefix, cin, cout, bn):
         self.prefix, self.cin, self.cout, self.bn = prefix, cin, cout, bn
@@ -389,9 +447,14 @@ class BlockSpec:
 
 class Trunk:
     """Native forward/backward of in_net_hv / in_net_id / out_net for the default flags
-    (k=2, BatchNorm on, non-cross).  `params` maps state_dict keys to device tensors."""
+    (BatchNorm on, non-cross) with 2x2 or 3x3 filters.  `params` maps state_dict keys to device tensors.
+    ksize 3 runs the exact-f32 3x3 kernels (conv3 / wgrad3): filters packed per layer, BatchNorm statistics by
+    mmlf_bn_stats_train, the data gradient's ReLU by `ref`, inference with BatchNorm folded into conv2."""
 
-    def __init__(self, chs, in_blocks, out_blocks, views, oc, momentum, eps=1e-5):
+    def __init__(self, chs, in_blocks, out_blocks, views, oc, momentum, eps=1e-5, ksize=2):
+        if ksize not in (2, 3):
+            raise ValueError(f'native trunk: ksize {ksize} (2 or 3)')
+        self.ksize = ksize
         self.chs, self.views, self.oc = chs, views, oc
         self.momentum, self.eps = float(momentum), float(eps)
         cin0 = views * 3
@@ -411,7 +474,7 @@ class Trunk:
     def _prepack(self, p, dev, with_dgrad):
         """every packed filter a step needs -- forward and, with_dgrad, data-gradient forms -- from ONE launch (f16 split
         only; the other modes pack per layer).  Keys: (parameter name, variant, dgrad)."""
-        if CONV_MODE != 'f16x3' or dev.type != 'cuda' or not BATCHED:
+        if CONV_MODE != 'f16x3' or dev.type != 'cuda' or not BATCHED or self.ksize != 2:
             return {}
         items = []
 
@@ -448,10 +511,12 @@ class Trunk:
         w1, b1 = p[f'{spec.prefix}.0.weight'], p[f'{spec.prefix}.0.bias']
         w2, b2 = p[f'{spec.prefix}.2.weight'], p[f'{spec.prefix}.2.bias']
         packs = packs or {}
-        thin = cmid <= THIN_MAX_N and spec.cin >= THIN_MIN_K        # the head: matrix-vector kernels, y is tiny
+        k3 = self.ksize == 3
+        pack = pack_filter3 if k3 else pack_filter
+        thin = cmid <= THIN_MAX_N and spec.cin >= THIN_MIN_K and not k3   # the head: matrix-vector kernels, y is tiny
         pk1 = packs.get((f'{spec.prefix}.0.weight', var, False))
         if pk1 is None and not thin:
-            pk1 = pack_filter(w1, var, False)
+            pk1 = pack(w1, var, False)
         folded = spec.bn and not train and rec_list is None        # inference: BatchNorm folded into conv2
         new_out = spec.bn and out is None                          # the block output is a buffer of its own
         got = geo.bufs([cs_mid] * ((1 if folded else 2) + (1 if new_out else 0)), dev)   # one zeroing launch for all
@@ -459,9 +524,12 @@ class Trunk:
         z = None if folded else got[1]
         if new_out:
             out, cs_out, c_off = got[-1], cs_mid, 0
-        ymask = geo.relu_mask(dev) if (rec_list is not None and CONV_MODE == 'f16x3' and not thin) else None
-        conv(geo, x, cs_x, spec.cin, pk1, b1, cmid, y, cs_mid, 0, H + 1, W + 1, True, mask_out=ymask, w_master=w1,
-             variant=var)
+        ymask = geo.relu_mask(dev) if (rec_list is not None and CONV_MODE == 'f16x3' and not thin and not k3) else None
+        if k3:
+            conv3(geo, x, cs_x, spec.cin, pk1, b1, cmid, y, cs_mid, True)
+        else:
+            conv(geo, x, cs_x, spec.cin, pk1, b1, cmid, y, cs_mid, 0, H + 1, W + 1, True, mask_out=ymask, w_master=w1,
+                 variant=var)
         if spec.bn and not train and rec_list is None:   # rec_list is None when nothing is saved for backward
             # inference: BatchNorm(eval) is a per-channel affine map -> fold it into conv2 and fuse the ReLU
             C = spec.cout
@@ -470,18 +538,24 @@ class Trunk:
                  ptr(p[f'{spec.prefix}.3.running_mean']), ptr(p[f'{spec.prefix}.3.running_var']), self.eps,
                  ptr(coef), ptr(coef[C:]), C, _lib.stream_ptr())
             w2f, b2f = torch.empty_like(w2), torch.empty_like(b2)
-            call('mmlf_fold_bn_eval', ptr(w2), ptr(b2), ptr(coef), ptr(coef[C:]), ptr(w2f), ptr(b2f), C, C,
-                 _lib.stream_ptr())
-            pk2 = pack_filter(w2f, var, False)
+            call('mmlf_fold_bn_eval3x3' if k3 else 'mmlf_fold_bn_eval', ptr(w2), ptr(b2), ptr(coef), ptr(coef[C:]), ptr(w2f),
+                 ptr(b2f), C, C, _lib.stream_ptr())
+            pk2 = pack(w2f, var, False)
             n_store = cs_out if new_out else C
-            conv(geo, y, cs_mid, cmid, pk2, b2f, cmid, out, cs_out, P + 1, H, W, True, n_store=n_store, out_off=c_off)
+            if k3:
+                conv3(geo, y, cs_mid, cmid, pk2, b2f, cmid, out, cs_out, True, n_store=n_store, out_off=c_off)
+            else:
+                conv(geo, y, cs_mid, cmid, pk2, b2f, cmid, out, cs_out, P + 1, H, W, True, n_store=n_store, out_off=c_off)
             return out, cs_out
         pk2 = packs.get((f'{spec.prefix}.2.weight', var, False))
         if pk2 is None:
-            pk2 = pack_filter(w2, var, False)
-        fused_stats = spec.bn and train and CONV_MODE == 'f16x3'      # statistics from the conv epilogue
-        conv(geo, y, cs_mid, cmid, pk2, b2, cmid, z, cs_mid, P + 1, H, W, False,
-             bn_partial=ws.partial if fused_stats else None)
+            pk2 = pack(w2, var, False)
+        fused_stats = spec.bn and train and CONV_MODE == 'f16x3' and not k3      # statistics from the conv epilogue
+        if k3:
+            conv3(geo, y, cs_mid, cmid, pk2, b2, cmid, z, cs_mid, False)
+        else:
+            conv(geo, y, cs_mid, cmid, pk2, b2, cmid, z, cs_mid, P + 1, H, W, False,
+                 bn_partial=ws.partial if fused_stats else None)
         rec = {'spec': spec, 'var': var, 'x': x, 'cs_x': cs_x, 'y': y, 'z': z, 'ymask': ymask}
         if not spec.bn:
             if rec_list is not None:
@@ -540,7 +614,7 @@ class Trunk:
             h = stacks[0]
             B, n, c, H, W = h.shape
             dev = h.device
-            geo = Geometry(B, H, W)
+            geo = Geometry(B, H, W, self.ksize)
             cin0 = n * c
         _Workspace.get(dev).enter_stream()
         packs = self._prepack(p, dev, save)
@@ -609,10 +683,11 @@ class Trunk:
         pre = spec.prefix
         sp = _lib.stream_ptr
         packs = packs or {}
+        k3 = self.ksize == 3
 
         def packed(name, w):
             pk = packs.get((name, var, True))
-            return pk if pk is not None else pack_filter(w, var, True)
+            return pk if pk is not None else (pack_filter3 if k3 else pack_filter)(w, var, True)
 
         # this block's gradient buffers, one zeroing launch: dz (behind BatchNorm), dy, dx
         got = geo.bufs(([cs_mid] if spec.bn else []) + [cs_mid] + ([cs_x] if need_dx else []), dev)
@@ -634,6 +709,17 @@ class Trunk:
         if after_bn:
             after_bn()
         w1, w2 = p[f'{pre}.0.weight'], p[f'{pre}.2.weight']
+        if k3:
+            # conv2: weight / bias gradient, data gradient fused with the ReLU of y; conv1: the same without the ReLU
+            wgrad3(geo, y, cs_mid, C, dz, cs_mid, C, grads[f'{pre}.2.weight'], grads[f'{pre}.2.bias'], var, ws.wgrad_ws(geo, C, C))
+            conv3(geo, dz, cs_mid, C, packed(f'{pre}.2.weight', w2), None, C, dy, cs_mid, False, ref=y, cs_ref=cs_mid)
+            del dz, got
+            wgrad3(geo, x, cs_x, spec.cin, dy, cs_mid, C, grads[f'{pre}.0.weight'], grads[f'{pre}.0.bias'], var,
+                   ws.wgrad_ws(geo, spec.cin, C))
+            if not need_dx:
+                return None
+            conv3(geo, dy, cs_mid, C, packed(f'{pre}.0.weight', w1), None, spec.cin, dx, cs_x, False)
+            return dx
         # conv2 (pad 0): weight/bias gradient, then data gradient fused with the ReLU mask of y
         wgrad(geo, y, cs_mid, C, dz, cs_mid, C, P + 1, grads[f'{pre}.2.weight'], grads[f'{pre}.2.bias'], var,
               ws.wgrad_ws(geo, C, C))
@@ -692,7 +778,7 @@ class Trunk:
 
         while recs:
             rec = recs.pop()
-            wide = OVERLAP_WGRAD and rec['spec'].cin >= 128
+            wide = OVERLAP_WGRAD and rec['spec'].cin >= 128 and self.ksize == 2
             res = self._block_bwd(geo, rec, p, grads, g, cs_g, 0, True, after_bn=settle, overlap=wide, packs=tape.get('packs'))
             settle()                        # (blocks without BatchNorm never called it)
             if wide:

@@ -146,7 +146,7 @@ class Ensamble(nn.Module):
                     from . import engine
                     _lib.load()
                     with torch.cuda.device(dev):
-                        geo = engine.Geometry(n, hh, ww)
+                        geo = engine.Geometry(n, hh, ww, inner._trunk.ksize)
                         cs = engine.cs_of(views * c)
                         xs = geo.bufs([cs] * 4, dev)
                         for kind, (t, x) in enumerate(zip(src, xs)):
