@@ -141,3 +141,71 @@ def test_the_product_library_says_what_it_is():
     assert f'abi={_lib.ABI_VERSION} ' in info and 'ablation=0' in info and 'MMLF_ABL_TERMS=3' in info
     assert 'MMLF_BOUNDS_DEBUG=0' in info and 'MMLF_GRID_PAD_W=2' in info
     assert lib().mmlf_build_is_ablation() == 0
+
+
+# ------------------------------------------------------------------ the 3x3 kernels (--model_ksize 3)
+# every (Cin, Cout) above, plus the DPP head widths the native predicate admits at other view counts (oc = 12 x views <= 288):
+# 132 (11 views: the third 96-column block of conv9tap_kernel lies wholly past N), 204 (17: partly live), 288 (24: full)
+LAYERS_K3 = LAYERS + [(280, 132), (280, 204), (280, 288)]
+CONV3 = dict(IN=0, PACKED=1, BIAS=2, OUT=3, REF=4)
+WG3 = dict(IN=0, G=1, GW=2, GB=3, WORKSPACE=4)
+
+
+def _k3_grid(L, B, H, W):
+    P = W + L.mmlf_grid_pad_w()
+    NQpad = L.mmlf_relu_mask_words(B, H, W) // 4096 * 256          # whole 256-position tiles ([tile][8][8][64] mask words)
+    return P, NQpad, L.mmlf_grid_alloc_positions_k3(B, H, W)
+
+
+@pytest.mark.parametrize('B,H,W', SHAPES)
+def test_conv3x3_launch_extents_fit_the_allocations_the_abi_prescribes(B, H, W):
+    L = lib()
+    P, NQpad, alloc = _k3_grid(L, B, H, W)
+    if B * (H + 2) * P + 2 * P + 600 >= 2 ** 31:
+        pytest.skip('engine.Geometry refuses this size')
+    # From conv9tap_kernel's index math: the last tile starts at NQpad - 256 and its window row dy = 2 starts 2P further on;
+    # the DMA pieces cover window positions 0..257 (lanes past it re-read 257).  The epilogue writes q + P + 1 for q < NQpad.
+    last_in = NQpad - 256 + 2 * P + 257
+    last_out = NQpad + P
+    for cin, cout in LAYERS_K3:
+        for dgrad in (False, True):
+            K, N = (cout, cin) if dgrad else (cin, cout)
+            cs_in, cs_out = cs_of(K), cs_of(N)
+            for n_store, c_off in ((cs_out, 0), (N, 0), (N, cs_out - N)):       # whole rows / exact channels / a channel slice
+                for cs_ref in (0, cs_out):
+                    e = (ctypes.c_int64 * 5)()
+                    assert L.mmlf_audit_conv3x3(cs_in, K, N, cs_out, n_store, cs_ref, B, H, W, e) == 0, _lib.last_error()
+                    tag = f'{K}->{N} B={B} {H}x{W} n_store={n_store} c_off={c_off} cs_ref={cs_ref}'
+                    assert (last_in + 1) * cs_in * 4 <= e[CONV3['IN']] <= alloc * cs_in * 4, tag
+                    assert e[CONV3['PACKED']] == L.mmlf_packed_filter3x3_floats(cs_in, N) * 4, tag
+                    assert e[CONV3['BIAS']] == N * 4, tag
+                    assert (last_out * cs_out + n_store) * 4 <= e[CONV3['OUT']] <= alloc * cs_out * 4 - c_off * 4, tag
+                    if cs_ref:
+                        assert (last_out * cs_ref + n_store) * 4 <= e[CONV3['REF']] <= alloc * cs_ref * 4, tag
+                    else:
+                        assert e[CONV3['REF']] == 0, tag
+
+
+@pytest.mark.parametrize('B,H,W', SHAPES)
+def test_wgrad3x3_launch_extents_fit_the_allocations_the_abi_prescribes(B, H, W):
+    L = lib()
+    P, NQpad, alloc = _k3_grid(L, B, H, W)
+    if B * (H + 2) * P + 2 * P + 600 >= 2 ** 31:
+        pytest.skip('engine.Geometry refuses this size')
+    # From wgrad9tap_kernel's index math: the last chunk starts at NQpad - 32; tap row dy = 2 stages its 32 positions and the
+    # two dx behind them from 2P on (rows 0..33), every channel of the last 32-channel slice below cs_in; the gradient tile is
+    # g[32 c + P + 1 .. + 31], every channel below cs_g.
+    last_in = NQpad - 32 + 2 * P + 33
+    last_g = NQpad + P
+    for pair in LAYERS_K3:
+        for cin, cout in (pair, pair[::-1]):
+            cs_in, cs_g = cs_of(cin), cs_of(cout)
+            ws = L.mmlf_wgrad3x3_workspace_floats(cin, cout, B, H, W) * 4
+            assert ws > 0
+            e = (ctypes.c_int64 * 5)()
+            assert L.mmlf_audit_wgrad3x3(cs_in, cin, cs_g, cout, B, H, W, e) == 0, _lib.last_error()
+            tag = f'{cin}->{cout} B={B} {H}x{W}'
+            assert (last_in + 1) * cs_in * 4 <= e[WG3['IN']] <= alloc * cs_in * 4, tag
+            assert (last_g + 1) * cs_g * 4 <= e[WG3['G']] <= alloc * cs_g * 4, tag
+            assert e[WG3['GW']] == cout * cin * 9 * 4 and e[WG3['GB']] == cout * 4, tag
+            assert e[WG3['WORKSPACE']] == ws, tag
