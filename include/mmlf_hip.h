@@ -44,10 +44,10 @@ const char *mmlf_last_error(void);
 #define MMLF_ABI_VERSION 9
 int mmlf_abi_version(void);
 
-/* What the binary is: one line with the ABI version, the source revision it was built from and the value of every build
- * switch that changes behaviour ("abi=7 git=... MMLF_ABL_TERMS=3 ... ablation=0").  mmlf_build_is_ablation() is nonzero for a
- * build that computes WRONG results by construction (the timing ablations, switches in csrc/conv_device.h): a binding must refuse such a
- * library unless its user asked for it (mmlf_amd/_lib.py: MMLF_ALLOW_ABLATION=1). */
+/* What the binary is: one line with the ABI version, the source revision it was built from and the bounds-debug switch
+ * ("abi=9 git=... src=... MMLF_BOUNDS_DEBUG=0 ablation=0").  mmlf_build_is_ablation() is nonzero for a build that computes
+ * WRONG results by construction (the timing ablations of older trees; the current sources have none and return 0): a
+ * binding must refuse such a library unless its user asked for it (mmlf_amd/_lib.py: MMLF_ALLOW_ABLATION=1). */
 const char *mmlf_build_info(void);
 int mmlf_build_is_ablation(void);
 /* compute units the persistent conv / weight-gradient launches size their grids by: the device's count, or the cap the
@@ -121,7 +121,7 @@ int mmlf_conv2x2_split(const float *in, int cs_in, int K, const void *packed, co
  * with the buffer's slack, before the tensor's first producer.
  * `packed` holds mmlf_packed_filter_h2_bytes(K, N) bytes (the columns' 1/scale factors sit behind the planes). */
 int64_t mmlf_amax_entries(int B, int H, int W);
-int mmlf_grid_pad_w(void);    /* grid pitch P = W + pad_w (2; a build option of the library, so the binding asks) */
+int mmlf_grid_pad_w(void);    /* grid pitch P = W + pad_w (2: the library's constant, which the binding asks for) */
 int mmlf_grid_pad_h(void);    /* grid rows per image R = H + pad_h (2) */
 int mmlf_amax_head(void);
 int mmlf_amax_shard_stride(void);

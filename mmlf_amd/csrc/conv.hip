@@ -67,9 +67,6 @@ struct ConvArgs {
     int a_pieces, seg_slot, seg_delta;   // split kernel: A window geometry (see conv4tap_x6s_kernel): 32-position pieces,
     int a_per_seg, a_tail;               // ... pieces per segment, positions the last piece of a segment has to fetch
     int nw;                              // waves per workgroup the launch uses (8, or 16: 512-position tiles)
-    int a_blocked;                       // round-6 proxy (MMLF_PROXY_BLOCKED_A=1, tools/kbench_blocked.py): `in` is a CHUNK-BLOCKED
-                                         // copy [tile][chunk of 8 channels][position][8 channels] of the NHWC tensor: one chunk of
-                                         // a window is one contiguous run of whole 128-byte lines, each fetched once
     const float *in_amax;                // f16 split: amax array of `in` (common.h): per-wave power-of-two operand scales
     const float *w_unscale;              // f16 split: 1 / (power-of-two scale of packed column n), [NP]
     float *out_amax;                     // optional: amax array of `out` (tensor and grid-row maxima, atomic max)
@@ -469,9 +466,7 @@ __device__ __forceinline__ void conv_epilogue16_tr(const ConvArgs &a, const f32x
                 asm("v_max_f32 %0, %1, |%2|" : "=v"(mk[mb]) : "v"(mk[mb]), "v"(v));
                 st[r] = __float_as_uint(v);
             }
-            // (MMLF_ABL_RS_FUSE, timing proxy: the 80-column kernels' pad-1 launches -- a stream block's first convolution -- store
-            //  nothing; the values are still formed, they feed the row maxima)
-            if (c0 < a.n_store && !(MMLF_ABL_RS_FUSE && G == 5 && a.out_shift == 0)) {
+            if (c0 < a.n_store) {
                 MMLF_OOB(OOB_OUT, (long long)lo + 64 * nb + (long long)(16 * mb) * a.cs_out * 4 + 12 >= ob_left);
                 __builtin_amdgcn_raw_buffer_store_b128(st, ob, lo + 64 * nb, (unsigned)(16 * mb) * a.cs_out * 4u, 0);
             }
@@ -578,14 +573,15 @@ __device__ __forceinline__ ConvArgs late_args()
 // are bound by memory concurrency, not by the matrix cores).  Layouts (masks, statistics, scales) are indexed by the
 // global 32-position group, so the two variants produce the same bytes.
 // TR: transposed accumulator tiles and epilogue (conv_epilogue16_tr above).
+constexpr int RING16 = 3;   // pipeline depth of the sixteen-wave variant (LDS: 30 KB per buffer + 20 KB; 4 measures the same)
 template <int G, int PL, int EPI = EPI_GENERIC, int NW = 8, bool TR = false>
 __global__ __launch_bounds__(64 * NW, (NW == 16 || G <= 6 ? 4 : 2)) void conv4tap_x6s_kernel(ConvArgs a, int ntiles)
 {
     constexpr int NP = G * 16;
     constexpr int TILE = 32 * NW;
-    // pipeline buffers: two; the sixteen-wave variant has the LDS for a ring of MMLF_RING16, with the DMA of chunk
+    // pipeline buffers: two; the sixteen-wave variant has the LDS for a ring of RING16, with the DMA of chunk
     // c + D - 1 issued during chunk c and a counted wait that leaves the newest D - 2 chunks' pieces in flight
-    constexpr int D = NW == 16 ? MMLF_RING16 : 2;
+    constexpr int D = NW == 16 ? RING16 : 2;
     // EARLY: the chunk's barrier stands two column blocks before its end (the weight fragments of those two blocks are
     // in registers by then): behind it the wave requests the NEXT chunk's activation and first weight fragments and runs
     // its last twelve MFMAs while they arrive -- the LDS latency of the chunk head (both waves of a SIMD stand in it at
@@ -622,12 +618,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 16 || G <= 6 ? 4 : 2)) void conv4ta
             for (int r = 0; r < 4; ++r) acc[mb][nb][r] = 0.f;
 
     // DMA addressing: a piece = wave-uniform 64-bit base (SGPRs) + one shared per-lane byte offset
-    // (chunk-blocked input, a.a_blocked: a piece is 32 positions x 32 bytes of ONE contiguous 1 KiB run -- lane l fetches bytes
-    //  [16 l, 16 l + 16); the tile's chunks are TILE x 32 bytes apart and slots >= TILE live in the next tile's block)
-    const bool blocked = (G == 5 && PL == 2) ? a.a_blocked != 0 : false;      // (the other widths: a compile-time false)
-    const unsigned voff_a = blocked ? (unsigned)lane * 16u
-                                    : ((unsigned)(lane >> 1) * (unsigned)a.cs_in + 4u * (lane & 1)) * 4u;   // A pieces
-    const unsigned a_chunk_stride = blocked ? (unsigned)TILE * 32u : 32u;
+    const unsigned voff_a = ((unsigned)(lane >> 1) * (unsigned)a.cs_in + 4u * (lane & 1)) * 4u;   // A pieces
     const unsigned voff_b = (unsigned)lane * 16u;                      // B pieces: linear
     const unsigned lds_base = (unsigned)(size_t)(lds_void_t *)smem;
     const char *in0 = reinterpret_cast<const char *>(a.in);
@@ -647,14 +638,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 16 || G <= 6 ? 4 : 2)) void conv4ta
         const int j = w + NW * k;
         const int seg = j >= a.a_per_seg, idx = j - seg * a.a_per_seg;   // two-segment mode: 320-slot segments
         const int slot = 320 * seg + 32 * idx;
-        a_src[k] = blocked ? (unsigned)(slot < TILE ? slot : a.nchunk * TILE + slot - TILE) * 32u
-                               : (unsigned)(slot + seg * a.seg_delta) * (unsigned)a.cs_in * 4u;
+        a_src[k] = (unsigned)(slot + seg * a.seg_delta) * (unsigned)a.cs_in * 4u;
         // bit 0 marks the last piece of a window (of a segment): only its first a_tail positions are ever read; the
         // other lanes re-fetch the last of those instead of positions nobody uses
         a_dst[k] = (unsigned)slot * 32u + (idx == a.a_per_seg - 1 ? 1u : 0u);
     }
-    const unsigned tail_lim = blocked ? (unsigned)(a.a_tail - 1) * 32u + 16u
-                                      : ((unsigned)(a.a_tail - 1) * (unsigned)a.cs_in + 4u) * 4u;
+    const unsigned tail_lim = ((unsigned)(a.a_tail - 1) * (unsigned)a.cs_in + 4u) * 4u;
     const unsigned b_src0 = 1024u * jb0, b_dst0 = (unsigned)(A_F4 + 64 * jb0) * 16u;
 
 #ifdef MMLF_BOUNDS_DEBUG      // the piece's last source byte against the buffer (the address is made scalar again for the asm)
@@ -676,7 +665,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 16 || G <= 6 ? 4 : 2)) void conv4ta
             const char *sb_;                                                                             \
             unsigned vo_, d_;                                                                            \
             if ((k) < nA) {                                                                              \
-                sb_ = in0 + (size_t)(tl) * tile_bytes + a_chunk_stride * (c) + a_src[(k) < 3 ? (k) : 0]; \
+                sb_ = in0 + (size_t)(tl) * tile_bytes + 32u * (c) + a_src[(k) < 3 ? (k) : 0];            \
                 d_ = a_dst[(k) < 3 ? (k) : 0];                                                           \
                 vo_ = min(voff_a, (d_ & 1u) ? tail_lim : 0xffffffffu);                                   \
                 d_ &= ~1u;                                                                               \
@@ -859,10 +848,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 16 || G <= 6 ? 4 : 2)) void conv4ta
                 X6_TERM(0, 1);
                 X6_TERM(0, 0);
             } else {
-                // MMLF_ABL_TERMS (ablation builds only, WRONG results): run 2 or 1 of the three cross terms with everything
-                // else unchanged -- the time a launch would take with fewer matrix instructions per product
-                if (MMLF_ABL_TERMS >= 3) H2_TERM(1, 0);
-                if (MMLF_ABL_TERMS >= 2) H2_TERM(0, 1);
+                H2_TERM(1, 0);
+                H2_TERM(0, 1);
                 H2_TERM(0, 0);
             }
 #undef X6_TERM
@@ -1009,19 +996,12 @@ __global__ __launch_bounds__(512, 2) void conv4tap_rs_kernel(ConvArgs a, int ngr
     const size_t row_off = (size_t)r16 * a.cs_in;                                     // floats
     const size_t rem_off = (size_t)((q4 & 1) + (q4 >> 1) * a.P) * a.cs_in + 32 * NS;
 
-    const int gi0 = gi;                                                               // (used by the MMLF_ABL_RS_FUSE proxy only)
     for (; gi < gend; gi += gstep) {
         const long long Q0 = (long long)(gi >> 3) * MMLF_TILE;
         const int wv = gi & 7;
-        // (MMLF_ABL_RS_FUSE, timing proxy: a pad-0 launch -- a stream block's second convolution -- reads the activations AND row
-        //  maxima of the wave's FIRST group every time: real values with real sparsity (the matrix cores' power follows the data),
-        //  served by the caches instead of memory, as a fused block's intermediate would be served by LDS)
-        const bool abl_reuse = MMLF_ABL_RS_FUSE && a.out_shift != 0;
-        const long long Qa = abl_reuse ? (long long)(gi0 >> 3) * MMLF_TILE : Q0;
-        const int wa = abl_reuse ? (gi0 & 7) : wv;
         // row maxima first (their loads are the oldest: the first counted wait below covers them)
-        const float gathered = wave_operand_amax_gather(a, Qa, wa, lane);
-        const float *p0 = a.in + (size_t)(Qa + 32 * wa) * a.cs_in + row_off;
+        const float gathered = wave_operand_amax_gather(a, Q0, wv, lane);
+        const float *p0 = a.in + (size_t)(Q0 + 32 * wv) * a.cs_in + row_off;
         float4 raw[NSTEP][2][2];                                   // [step][row block][half]
 #pragma unroll
         for (int k = 0; k < NSTEP; ++k) {
@@ -1391,13 +1371,11 @@ static bool conv_sixteen_waves(int planes, int np, const Grid &g)
 // The transposed epilogue (conv_epilogue16_tr) serves the launch kinds plain / ReLU / ReLU + mask-out / mask-in when the
 // output rows can take 16-byte stores.  MMLF_CONV_TR=0 turns it off for the whole process (A/B; the ReLU mask words then
 // have the other layout, for their producer and their consumer alike).
-static int conv_tr_mode()
+static bool conv_tr_enabled()
 {
     static const int on = [] { const char *e = getenv("MMLF_CONV_TR"); return e ? atoi(e) : 1; }();
-    return on;
+    return on != 0;
 }
-static bool conv_tr_enabled() { return conv_tr_mode() != 0; }
-static bool conv_tr_any_shape() { return conv_tr_mode() == 2; }     // 2: also where the geometry rule says no (A/B)
 static bool conv_tr_fits(const ConvArgs &a)
 {
     return a.n_store % 4 == 0 && a.cs_out % 4 == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
@@ -1416,7 +1394,7 @@ static int launch_conv_x6s_epi(const ConvArgs &a, long long ntiles, hipStream_t 
     if constexpr (PL == 2 && G == 5) {
         if (a.nw == 16) {
             constexpr size_t lds_stats16 = 16 * (G * 16) * 2 * sizeof(double);
-            constexpr size_t lds_pipe16 = MMLF_RING16 * (2 * 640 + 4 * PL * G * 16) * sizeof(float4);
+            constexpr size_t lds_pipe16 = RING16 * (2 * 640 + 4 * PL * G * 16) * sizeof(float4);
             static PerDeviceOnce attr_once16;
             if (attr_once16.run([] { return mmlf_allow_lds(reinterpret_cast<const void *>(conv4tap_x6s_kernel<G, PL, EPI, 16, TR>),
                                                            lds_pipe16 + (TR ? lds_coef : lds_stats16), "mmlf_conv2x2_h2(16 waves)"); }))
@@ -1512,7 +1490,7 @@ static int launch_conv_x6s(const ConvArgs &a, long long ntiles, hipStream_t st)
         const long long n = ntiles;
         if (a.ref && !a.relu && !a.bn_partial && !a.relu_mask_in && !a.relu_mask_out)
             return launch_conv_x6s_epi<G, PL, EPI_REF_IN>(a, n, st);
-        MMLF_CONV_KIND_SWITCH(launch_conv_x6s_epi, G == 18, G != 18 || a.seg_delta == 0 || conv_tr_any_shape(), G, PL);
+        MMLF_CONV_KIND_SWITCH(launch_conv_x6s_epi, G == 18, G != 18 || a.seg_delta == 0, G, PL);
     }
     // (other widths: the generic build, whose mask words have conv_epilogue16's layout for producer and consumer alike)
     return launch_conv_x6s_epi<G, PL, EPI_GENERIC>(a, ntiles, st);
@@ -1573,11 +1551,6 @@ static int conv_split_impl(const char *who, int planes, const float *in, int cs_
         a.a_per_seg = 9; a.a_pieces = 18; a.seg_slot = 320; a.seg_delta = g.P - 320;
     }
     a.a_tail = (a.seg_delta ? 257 : g.P + tile + 1) - 32 * (a.a_per_seg - 1);
-    {   // round-6 proxy: the caller passes a chunk-blocked copy of the input (see ConvArgs::a_blocked); tiled 80-column kernel only
-        const char *e = getenv("MMLF_PROXY_BLOCKED_A");
-        a.a_blocked = (e && atoi(e) && planes == 2 && np == 80 && a.seg_delta == 0 && !conv_rs_shape(planes, np, a.nchunk, a.nw)) ? 1 : 0;
-        MMLF_CHECK_ARG(!(e && atoi(e)) || a.a_blocked, "%s: MMLF_PROXY_BLOCKED_A is set but this launch has no chunk-blocked form", who);
-    }
     const long long ntiles = g.NQpad / tile;
     hipStream_t st = (hipStream_t)stream;
     return planes == 3 ? launch_conv_split<3>(np, a, ntiles, st) : launch_conv_split<2>(np, a, ntiles, st);
@@ -1787,8 +1760,10 @@ extern "C" int mmlf_conv2x2_thin(const float *in, int cs_in, int K, const float 
 }
 
 // ---------------------------------------------------------------------------------------------
-// what this binary is (round 5): every build switch that changes behaviour, in one string; the loader refuses a
-// result-changing build unless told otherwise (mmlf_amd/_lib.py), bench.py prints the string in its line
+// what this binary is (round 5): ABI version, source revision and the bounds-debug switch in one string; bench.py prints it in
+// its line.  The product sources have no result-changing build switch any more (tools/README.md "Removed", EXPERIMENTS.md),
+// so mmlf_build_is_ablation() is 0 here; the loader still refuses a variant built from an older tree that reports 1
+// (mmlf_amd/_lib.py)
 // ---------------------------------------------------------------------------------------------
 #ifndef MMLF_GIT_HASH
 #define MMLF_GIT_HASH "unknown"
@@ -1798,17 +1773,14 @@ extern "C" int mmlf_conv2x2_thin(const float *in, int cs_in, int K, const float 
 #else
 #define MMLF_BOUNDS_DEBUG_VALUE 0
 #endif
-extern "C" int mmlf_build_is_ablation(void) { return (MMLF_ABL_TERMS != 3 || MMLF_ABL_WGRAD_STAGE != 0 || MMLF_ABL_RS_FUSE != 0) ? 1 : 0; }
+extern "C" int mmlf_build_is_ablation(void) { return 0; }
 extern "C" const char *mmlf_build_info(void)
 {
     static char text[448];
     static std::once_flag once;
     std::call_once(once, [] {
-        snprintf(text, sizeof(text),
-                 "abi=%d git=%s src=%s MMLF_ABL_TERMS=%d MMLF_ABL_WGRAD_STAGE=%d MMLF_ABL_RS_FUSE=%d MMLF_GRID_PAD_W=%d MMLF_GRID_PAD_H=%d MMLF_RING16=%d "
-                 "MMLF_WGRAD_EARLY=%d MMLF_WGRADN_CLAMP=%d MMLF_WGRAD_ZEROPAD=%d MMLF_BOUNDS_DEBUG=%d ablation=%d",
-                 MMLF_ABI_VERSION, MMLF_GIT_HASH, MMLF_SRC_HASH, MMLF_ABL_TERMS, MMLF_ABL_WGRAD_STAGE, MMLF_ABL_RS_FUSE, MMLF_GRID_PAD_W, MMLF_GRID_PAD_H,
-                 MMLF_RING16, MMLF_WGRAD_EARLY, MMLF_WGRADN_CLAMP, MMLF_WGRAD_ZEROPAD, MMLF_BOUNDS_DEBUG_VALUE, mmlf_build_is_ablation());
+        snprintf(text, sizeof(text), "abi=%d git=%s src=%s MMLF_BOUNDS_DEBUG=%d ablation=%d", MMLF_ABI_VERSION, MMLF_GIT_HASH,
+                 MMLF_SRC_HASH, MMLF_BOUNDS_DEBUG_VALUE, mmlf_build_is_ablation());
     });
     return text;
 }

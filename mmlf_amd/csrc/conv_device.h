@@ -1,5 +1,5 @@
 // conv_device.h -- what the convolution (conv.hip) and weight-gradient (wgrad.hip) translation units share: vector types,
-// the build switches, operand splits, buffer-descriptor helpers, the compute-unit count the persistent grids are sized by.
+// operand splits, buffer-descriptor helpers, the compute-unit count the persistent grids are sized by.
 #pragma once
 #include <cstdlib>
 #include <stdlib.h>
@@ -26,46 +26,14 @@ __device__ __forceinline__ int mmlf_records_left(long long total, long long off)
     return (int)((left16 < 0x7ffffffu ? left16 : 0x7ffffffu) << 4);
 }
 
-// Build switches.  Round 5 removed the timing-ablation switches of rounds 3-4 whose experiments are closed (their numbers
-// stay in EXPERIMENTS.md 4.7-4.8: half weight-fragment reads, double split, pre-split operand, 32x32x16 tiles, no early
-// barrier, non-temporal activation DMA, wave priorities, the narrow kernel's timeline; check out round 4's tree to rebuild
-// them).  What is left changes either nothing observable (MMLF_RING16, MMLF_WGRAD_EARLY, MMLF_WGRADN_CLAMP, MMLF_WGRAD_ZEROPAD:
-// tuning constants and equivalent forms) or the RESULT:
-//   MMLF_ABL_TERMS < 3 -- run only 2 or 1 of the f16 split's three cross terms (a timing ablation: WRONG results);
-//   MMLF_ABL_WGRAD_STAGE -- timing ablations of the wide weight gradient's staging (below: WRONG results);
-//   MMLF_ABL_RS_FUSE -- timing proxy of a fused evaluation stream block (below: WRONG results).
-// mmlf_build_info() reports every one of them and the Python loader refuses a library with a result-changing switch
-// unless MMLF_ALLOW_ABLATION=1 is set (mmlf_amd/_lib.py).
-#ifndef MMLF_ABL_TERMS
-#define MMLF_ABL_TERMS 3     // cross terms of the f16 split that are evaluated (3 = the arithmetic; fewer: timing ablation)
-#endif
-#ifndef MMLF_ABL_WGRAD_STAGE
-#define MMLF_ABL_WGRAD_STAGE 0   // wide weight gradient, timing ablations of its staging (WRONG results): 1 = the gradient tile
-#endif                           // is stored unsplit (loads and LDS stores stay, no vector work on it: what a producer-side split
-                                 // could save at most); 2 = it is neither loaded nor stored after the first chunk (what staging
-                                 // it ONCE per chunk for all six slices could save at most); 3 = nothing is staged after the first
-                                 // chunk (matrix instructions, fragment reads and the barrier alone)
-#ifndef MMLF_ABL_RS_FUSE
-#define MMLF_ABL_RS_FUSE 0       // round-6 timing proxy of a FUSED evaluation stream block (WRONG results): in the register-streamed
-#endif                           // narrow kernel, pad-1 launches (a block's first convolution) store nothing and pad-0 launches (its
-                                 // second) load no activations -- what conv(p1)+ReLU+conv(p0) of a block could cost at the very least
-                                 // if the intermediate never left the CU (the exchange through LDS is NOT counted): EXPERIMENTS.md 4.10
-#ifndef MMLF_RING16
-#define MMLF_RING16 3   // pipeline depth of the sixteen-wave conv variant (LDS: 30 KB per buffer + 20 KB; 4 measures the same)
-#endif
+// No build switch changes what these kernels compute or how: the timing ablations, proxies and A/B forms of closed
+// experiments left the sources with them (rounds 3-4 in round 5, the rest after round 6: tools/README.md "Removed"; their
+// numbers stay in EXPERIMENTS.md, their logs under profiles/).  -DMMLF_BOUNDS_DEBUG (common.h) is the one option left that
+// changes the code.
 #define MMLF_BUF_FLAGS 0x00020000   // raw dword buffer (DATA_FORMAT_32), no swizzle
 // (round 5 measured the epilogue's stores with the non-temporal policy on the 80-column kernels, whose activation lines compete
 // with their own output for an XCD's L2: +12...20 % time on every launch kind, profiles/r05_kbench_nt_store.log -- the L2 is what
 // merges the two 64-byte halves of an output line that two store instructions write; the switch was removed again)
-#ifndef MMLF_WGRAD_EARLY
-#define MMLF_WGRAD_EARLY 1     // the wide weight gradient's early barrier + next-chunk fragment prefetch (16 VGPRs)
-#endif
-#ifndef MMLF_WGRADN_CLAMP
-#define MMLF_WGRADN_CLAMP 1    // narrow weight gradient: staging items and channels past the tile are clamped, not predicated (wgrad.hip)
-#endif
-#ifndef MMLF_WGRAD_ZEROPAD
-#define MMLF_WGRAD_ZEROPAD 0   // wide weight gradient: 1 = padding channels staged as zeros behind selects (round 4's form; wgrad.hip)
-#endif
 #ifndef MMLF_SRC_HASH
 #define MMLF_SRC_HASH "unknown"     // content hash of csrc/*.hip, csrc/*.h and include/mmlf_hip.h (csrc/build.py, tools/build_variant.sh)
 #endif

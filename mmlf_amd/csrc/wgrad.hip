@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void wgrad4tap_x6n_kernel(WgradArgs a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[mb][nb][r] = 0.f;
 
-    // MMLF_WGRADN_CLAMP (round 5): staging items and channels past the tile are CLAMPED -- surplus threads load and store the last
+    // Staging items and channels past the tile are CLAMPED (round 5) -- surplus threads load and store the last
     // item again, padding channels are copies of the tensor's last four -- instead of predicated and zero-filled: no divergent
     // branch per piece; the padding only feeds accumulator rows / columns the reduction never reads (as in the wide kernel).
     float4 ra[NA], rg[NG];
@@ -356,49 +356,39 @@ __global__ __launch_bounds__(256, 2) void wgrad4tap_x6n_kernel(WgradArgs a)
     do {                                                                                                    \
         const long long Qc = (long long)(c) * WG_KQ;                                                        \
         _Pragma("unroll") for (int j = 0; j < NA; ++j) {                                                    \
-            const int idx = MMLF_WGRADN_CLAMP ? min(tid + 256 * j, 66 * FA - 1) : tid + 256 * j;            \
+            const int idx = min(tid + 256 * j, 66 * FA - 1);                                                \
             const int row = idx / FA, f = idx - row * FA;                                                   \
             const int seg = row >= 33, pix = row - 33 * seg;                                                \
-            const int ch = MMLF_WGRADN_CLAMP ? min(ci0 + 4 * f, a.cs_in - 4) : ci0 + 4 * f;                 \
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);                                                     \
-            MMLF_OOB(OOB_WG_IN, idx < 66 * FA && ch < a.cs_in && ((Qc + seg * a.P + pix) * a.cs_in + ch + 4) * 4ll > a.in_bytes); \
-            if (MMLF_WGRADN_CLAMP || (idx < 66 * FA && ch < a.cs_in))                                       \
-                v = *reinterpret_cast<const float4 *>(a.in + (size_t)(Qc + seg * a.P + pix) * a.cs_in + ch); \
-            ra[j] = v;                                                                                      \
+            const int ch = min(ci0 + 4 * f, a.cs_in - 4);                                                   \
+            MMLF_OOB(OOB_WG_IN, ((Qc + seg * a.P + pix) * a.cs_in + ch + 4) * 4ll > a.in_bytes);            \
+            ra[j] = *reinterpret_cast<const float4 *>(a.in + (size_t)(Qc + seg * a.P + pix) * a.cs_in + ch); \
         }                                                                                                   \
         _Pragma("unroll") for (int j = 0; j < NG; ++j) {                                                    \
-            const int idx = MMLF_WGRADN_CLAMP ? min(tid + 256 * j, WG_KQ * FG - 1) : tid + 256 * j;         \
+            const int idx = min(tid + 256 * j, WG_KQ * FG - 1);                                             \
             const int row = idx / FG, f = idx - row * FG;                                                   \
-            const int gc = MMLF_WGRADN_CLAMP ? min(4 * f, a.cs_g - 4) : 4 * f;                              \
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);                                                     \
-            MMLF_OOB(OOB_WG_G, idx < WG_KQ * FG && gc < a.cs_g && ((Qc + a.g_shift + row) * a.cs_g + gc + 4) * 4ll > a.g_bytes); \
-            if (MMLF_WGRADN_CLAMP || (idx < WG_KQ * FG && 4 * f < a.cs_g))                                  \
-                v = *reinterpret_cast<const float4 *>(a.g + (size_t)(Qc + a.g_shift + row) * a.cs_g + gc);  \
-            rg[j] = v;                                                                                      \
+            const int gc = min(4 * f, a.cs_g - 4);                                                          \
+            MMLF_OOB(OOB_WG_G, ((Qc + a.g_shift + row) * a.cs_g + gc + 4) * 4ll > a.g_bytes);               \
+            rg[j] = *reinterpret_cast<const float4 *>(a.g + (size_t)(Qc + a.g_shift + row) * a.cs_g + gc);  \
         }                                                                                                   \
     } while (0)
 #define WN_LSTORE()                                                                                         \
     do {                                                                                                    \
         _Pragma("unroll") for (int j = 0; j < NA; ++j) {                                                    \
-            const int idx = MMLF_WGRADN_CLAMP ? min(tid + 256 * j, 66 * FA - 1) : tid + 256 * j;            \
-            if (MMLF_WGRADN_CLAMP || idx < 66 * FA) {                                                       \
-                const int row = idx / FA, f = idx - row * FA;                                               \
-                const int seg = row >= 33, pix = row - 33 * seg;                                            \
-                float4 v = ra[j];         /* ones row (bias gradient): patched here, not at load time, */ \
-                const int ch = ci0 + 4 * f; /* so that the global loads issue back to back               */ \
-                if (ch == a.cin) v.x = sc.inv_sa;   /* = 1 after scaling */                                 \
-                if (ch + 1 == a.cin) v.y = sc.inv_sa;                                                       \
-                if (ch + 2 == a.cin) v.z = sc.inv_sa;                                                       \
-                if (ch + 3 == a.cin) v.w = sc.inv_sa;                                                       \
-                split_store4_pl<PL>(v, st_sa, As + seg * PL * A_PLANE + pix * ROWA + 8 * f, A_PLANE);       \
-            }                                                                                               \
+            const int idx = min(tid + 256 * j, 66 * FA - 1);                                                \
+            const int row = idx / FA, f = idx - row * FA;                                                   \
+            const int seg = row >= 33, pix = row - 33 * seg;                                                \
+            float4 v = ra[j];         /* ones row (bias gradient): patched here, not at load time, */       \
+            const int ch = ci0 + 4 * f; /* so that the global loads issue back to back               */     \
+            if (ch == a.cin) v.x = sc.inv_sa;   /* = 1 after scaling */                                     \
+            if (ch + 1 == a.cin) v.y = sc.inv_sa;                                                           \
+            if (ch + 2 == a.cin) v.z = sc.inv_sa;                                                           \
+            if (ch + 3 == a.cin) v.w = sc.inv_sa;                                                           \
+            split_store4_pl<PL>(v, st_sa, As + seg * PL * A_PLANE + pix * ROWA + 8 * f, A_PLANE);           \
         }                                                                                                   \
         _Pragma("unroll") for (int j = 0; j < NG; ++j) {                                                    \
-            const int idx = MMLF_WGRADN_CLAMP ? min(tid + 256 * j, WG_KQ * FG - 1) : tid + 256 * j;         \
-            if (MMLF_WGRADN_CLAMP || idx < WG_KQ * FG) {                                                    \
-                const int row = idx / FG, f = idx - row * FG;                                               \
-                split_store4_pl<PL>(rg[j], st_sg, Gs + row * ROWG + 8 * f, G_PLANE);                        \
-            }                                                                                               \
+            const int idx = min(tid + 256 * j, WG_KQ * FG - 1);                                             \
+            const int row = idx / FG, f = idx - row * FG;                                                   \
+            split_store4_pl<PL>(rg[j], st_sg, Gs + row * ROWG + 8 * f, G_PLANE);                            \
         }                                                                                                   \
     } while (0)
     // transposed-read geometry: lane 4q+p of a 16-lane group addresses row q, columns 4p..4p+3
@@ -517,8 +507,8 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
     // Input channels past cs_in and gradient columns past cs_g (the slices' and the 288 columns' padding) are staged as COPIES of
     // the tensor's last four channels (the clamped load) instead of zeros: they only feed accumulator rows / columns that
     // wgrad_reduce_kernel never reads (ci > Cin, co >= Cout), the copies are in-range values (no f16 overflow), and the ones row
-    // (ci == Cin) is patched in WW_STORE_A either way.  Four selects per staging piece less (round 5;
-    // -DMMLF_WGRAD_ZEROPAD=1 builds the zero-filling form: profiles/r05_kbench_wgrad_zeropad.log).
+    // (ci == Cin) is patched in WW_STORE_A either way.  Four selects per staging piece less (round 5; the zero-filling form:
+    // profiles/r05_kbench_wgrad_zeropad.log).
 
     // staging items are clamped to the last one instead of predicated: surplus threads load and store that
     // item again (same value), which keeps the loop free of branches.  Also of SCALAR ones: round 5 let the waves whose
@@ -559,8 +549,7 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
         /* 32-bit offset as is -- no vector address arithmetic, and the address unit range-checks the access          */ \
         const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc(                               \
             const_cast<char *>(in_b + cb_), 0, mmlf_records_left(a.in_bytes, cb_), MMLF_BUF_FLAGS);         \
-        const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_, ga_off[j], 0, 0)); \
-        ra[j] = (MMLF_WGRAD_ZEROPAD && !(a_ch[j] < a.cs_in)) ? make_float4(0.f, 0.f, 0.f, 0.f) : v;         \
+        ra[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_, ga_off[j], 0, 0));    \
     } while (0)
 #define WW_GLOAD_G(j, c)                                                                                    \
     do {                                                                                                    \
@@ -568,8 +557,7 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
         MMLF_OOB(OOB_WG_G, cb_ + gg_off[j] + 16 > a.g_bytes);                                               \
         const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc(                               \
             const_cast<char *>(g_b + cb_), 0, mmlf_records_left(a.g_bytes, cb_), MMLF_BUF_FLAGS);           \
-        const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_, gg_off[j], 0, 0)); \
-        rg[j] = (MMLF_WGRAD_ZEROPAD && !(lg_off[j] - A_BYTES - (lg_off[j] - A_BYTES) / ROWG * ROWG < 2 * a.cs_g)) ? make_float4(0.f, 0.f, 0.f, 0.f) : v; \
+        rg[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_, gg_off[j], 0, 0));    \
     } while (0)
 #define WW_GLOAD(c)                                                                                         \
     do {                                                                                                    \
@@ -586,16 +574,7 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
         v.w = ch + 3 == a.cin ? sc.inv_sa : v.w;                                                            \
         split_store4_pl<PL>(v, st_sa, (dst) + la_off[j], A_PLANE);                                          \
     } while (0)
-#define WW_STORE_G(j, dst)                                                                                  \
-    do {                                                                                                    \
-        if (MMLF_ABL_WGRAD_STAGE == 1 && PL == 2) {      /* ablation: the same bytes, no split */            \
-            char *p0_ = (dst) + lg_off[j];                                                                  \
-            *reinterpret_cast<uint2 *>(p0_) = make_uint2(__float_as_uint(rg[j].x), __float_as_uint(rg[j].y)); \
-            *reinterpret_cast<uint2 *>(p0_ + G_PLANE) = make_uint2(__float_as_uint(rg[j].z), __float_as_uint(rg[j].w)); \
-        } else {                                                                                            \
-            split_store4_pl<PL>(rg[j], st_sg, (dst) + lg_off[j], G_PLANE);                                  \
-        }                                                                                                   \
-    } while (0)
+#define WW_STORE_G(j, dst) split_store4_pl<PL>(rg[j], st_sg, (dst) + lg_off[j], G_PLANE)
 
     const int tq = (lane & 15) >> 2, tp = lane & 3;
     const int a_off = (t >> 1) * PL * A_PLANE + ((t & 1) + 4 * q4 + tq) * ROWA + 8 * tp;
@@ -616,7 +595,7 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
         // store of the chunk is out by then (one piece per column block, NA + NG <= NBH - 2) and every fragment read
         // requested -- and behind it the wave asks for the NEXT chunk's first gradient fragments (the rotating slots run
         // on, NBH % 3 == 0) and its first two activation row blocks, which arrive under the last 2 x 3 x MB MFMAs.
-        constexpr bool EARLY = MMLF_WGRAD_EARLY && PL == 2 && NBH % 3 == 0 && NA + NG <= NBH - 2 && MB >= 2;
+        constexpr bool EARLY = PL == 2 && NBH % 3 == 0 && NA + NG <= NBH - 2 && MB >= 2;
         bf16x8 af[MB][PL], gfr[3][PL], afp[2][PL];
         if constexpr (EARLY) {
             const char *cur0 = smem;
@@ -666,18 +645,14 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
             }                                                                                                \
             if (STAGE) {                                                                                     \
                 if (nb < NA) {                                                                               \
-                    if (MMLF_ABL_WGRAD_STAGE < 3) {                                                          \
-                        WW_STORE_A(nb < NA ? nb : 0, nxt);                                                   \
-                        if (RELOAD) WW_GLOAD_A(nb < NA ? nb : 0, c + 2);                                     \
-                    }                                                                                        \
+                    WW_STORE_A(nb < NA ? nb : 0, nxt);                                                       \
+                    if (RELOAD) WW_GLOAD_A(nb < NA ? nb : 0, c + 2);                                         \
                 } else if (nb - NA < NG) {                                                                   \
-                    if (MMLF_ABL_WGRAD_STAGE < 2) {                                                          \
-                        WW_STORE_G(nb - NA < NG ? nb - NA : 0, nxt);                                         \
-                        if (RELOAD) WW_GLOAD_G(nb - NA < NG ? nb - NA : 0, c + 2);                           \
-                    }                                                                                        \
+                    WW_STORE_G(nb - NA < NG ? nb - NA : 0, nxt);                                             \
+                    if (RELOAD) WW_GLOAD_G(nb - NA < NG ? nb - NA : 0, c + 2);                               \
                 }                                                                                            \
             }                                                                                                \
-            _Pragma("unroll") for (int term = (PL == 3 ? 0 : 3 - MMLF_ABL_TERMS); term < (PL == 3 ? 6 : 3); ++term) \
+            _Pragma("unroll") for (int term = 0; term < (PL == 3 ? 6 : 3); ++term)                           \
                 WW_TERM(gfr[nb % 3], term_a<PL>(term), term_b<PL>(term));                                    \
         }                                                                                                    \
         if (EARLY && (STAGE)) {                                                                              \
@@ -829,9 +804,6 @@ static inline bool wgrad16_cfg(int Cin, int Cout, long long nchunks, Wgrad16Cfg 
         const int one_round = cus / c->nslice, three_rounds = (768 / c->nslice + 7) / 8 * 8;
         c->nsplit = nchunks < 0 ? (one_round > three_rounds ? one_round : three_rounds)
                                 : (nchunks >= 42 * 1024 ? three_rounds : one_round);
-        static const int forced = [] { const char *e = getenv("MMLF_WGRAD_NSPLIT"); return e ? atoi(e) : 0; }();
-        if (forced > 0 && nchunks >= 0)                          // A/B switch (tools/ab_env.sh), inside the sized workspace
-            c->nsplit = forced <= (three_rounds > one_round ? three_rounds : one_round) ? forced : c->nsplit;
         if (c->nsplit < 8) c->nsplit = 8;
     } else {                     // wgrad4tap_x6n_kernel: two 256-thread workgroups per CU
         c->mb = (c->nb <= 5 && Cin + 1 > 32 && Cin + 1 <= 80) ? 5 : 2;

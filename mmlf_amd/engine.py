@@ -30,7 +30,7 @@ class Geometry:
     def __init__(self, B, H, W, ksize=2):
         self.B, self.H, self.W = B, H, W
         self.ksize = ksize
-        # pitch W + 2, H + 2 rows (the library's build options MMLF_GRID_PAD_W / _H: csrc/common.h has the measured alternatives)
+        # pitch W + 2, H + 2 rows (the library reports its constant; csrc/common.h has the measured alternatives)
         self.P, self.R = W + int(_lib.load().mmlf_grid_pad_w()), H + int(_lib.load().mmlf_grid_pad_h())
         self.G = self.P * self.R
         self.NQ = B * self.G
@@ -56,8 +56,6 @@ class Geometry:
     def bufs(self, css, device):
         """several grid buffers (channel strides `css`, at most four) whose slack and amax arrays ONE launch zeroes"""
         assert 1 <= len(css) <= 4
-        if not BATCHED:
-            return [self.buf(cs, device) for cs in css]
         ts = []
         for cs in css:
             t = torch.empty(self.alloc * cs, dtype=torch.float32, device=device)
@@ -258,10 +256,6 @@ def _amax_of(geo, t, cs):
 
 
 CHECK_ABSMAX = bool(os.environ.get('MMLF_CHECK_ABSMAX'))
-# one launch packs every filter of a step / zeroes the slack of a block's buffers (0: per filter, per buffer)
-BATCHED = os.environ.get('MMLF_BATCHED', '1') != '0'
-# one BatchNorm-apply pass for the four streams' last blocks (whole rows of the concat buffer); 0: four slice passes
-APPLY4 = os.environ.get('MMLF_APPLY4', '1') != '0'
 # MMLF_OVERLAP_WGRAD (default 1 since round 6; 0 switches it off): conv1's weight gradient of the wide blocks runs on a side
 # stream beside the BatchNorm-backward kernels of the block underneath (which only need the data gradient).  It pays since the
 # weight gradient is down to 2 x 232 registers per SIMD and both BatchNorm-backward kernels fit the 48 left (round 5:
@@ -474,7 +468,7 @@ class Trunk:
     def _prepack(self, p, dev, with_dgrad):
         """every packed filter a step needs -- forward and, with_dgrad, data-gradient forms -- from ONE launch (f16 split
         only; the other modes pack per layer).  Keys: (parameter name, variant, dgrad)."""
-        if CONV_MODE != 'f16x3' or dev.type != 'cuda' or not BATCHED or self.ksize != 2:
+        if CONV_MODE != 'f16x3' or dev.type != 'cuda' or self.ksize != 2:
             return {}
         items = []
 
@@ -628,7 +622,7 @@ class Trunk:
         # the four streams' last BatchNorm-apply passes write quarter rows of the concat buffer: one pass for all four
         # (whole rows) when they are real passes (not folded into conv2) and the channel count allows it
         fold = not train and not save
-        deferred = [] if (APPLY4 and not fold and self.chs % 2 == 0 and all(b[-1].bn for _, _, b in self.streams)) else None
+        deferred = [] if (not fold and self.chs % 2 == 0 and all(b[-1].bn for _, _, b in self.streams)) else None
         for s, (key, var, blocks) in enumerate(self.streams):
             x = xs[s]
             if packed is None:

@@ -138,8 +138,13 @@ def test_loader_refuses_other_abi_versions_and_anonymous_builds():
 
 def test_the_product_library_says_what_it_is():
     info = _lib.build_info()
-    assert f'abi={_lib.ABI_VERSION} ' in info and 'ablation=0' in info and 'MMLF_ABL_TERMS=3' in info
-    assert 'MMLF_BOUNDS_DEBUG=0' in info and 'MMLF_GRID_PAD_W=2' in info
+    assert f'abi={_lib.ABI_VERSION} ' in info and 'ablation=0' in info
+    assert 'MMLF_BOUNDS_DEBUG=0' in info
+    retired = ('MMLF_ABL_TERMS', 'MMLF_ABL_WGRAD_STAGE', 'MMLF_ABL_RS_FUSE', 'MMLF_PROXY_BLOCKED_A', 'MMLF_RING16',
+               'MMLF_WGRAD_EARLY', 'MMLF_WGRADN_CLAMP', 'MMLF_WGRAD_ZEROPAD', 'MMLF_GRID_PAD_W', 'MMLF_GRID_PAD_H',
+               'MMLF_WGRAD_NSPLIT', 'MMLF_PACK_LDS_KB', 'MMLF_BATCHED', 'MMLF_APPLY4')
+    assert not [name for name in retired if name in info], info
+    assert lib().mmlf_grid_pad_w() == 2 and lib().mmlf_grid_pad_h() == 2
     assert lib().mmlf_build_is_ablation() == 0
 
 
