@@ -152,25 +152,18 @@ static inline int pick_nt(int N)
     return -1;
 }
 
-// master-filter tap for (packed tap t, variant): returns sy*2+sx into the OIHW (.,.,2,2) master
+// master-filter tap for (packed tap t, variant) of a KS x KS filter: packed tap t = dy*KS + dx (the launch reads
+// q + dy*P + dx) -> sy*KS+sx into the OIHW (.,.,KS,KS) master.  The stream nets of the H / I stacks run on the transposed
+// (and, for I, then flipped) image (reference feed_forward.py:236-256): the transposed image is served by the transposed
+// filter and the flipped one by sx = KS-1 - dy (tests/test_gpu_ksize3.py pins all three 3x3 forms against nn.Conv2d on the
+// transformed image).
+template <int KS>
 __host__ __device__ static inline int master_tap(int t, int variant)
 {
-    const int dy = t >> 1, dx = t & 1;
-    if (variant == 0) return dy * 2 + dx;         // identity
-    if (variant == 1) return dx * 2 + dy;         // transpose
-    return dx * 2 + (1 - dy);                     // transpose, then flip along kernel-H
-}
-
-// the same for the 3x3 filters: packed tap t = dy*3 + dx (the launch reads q + dy*P + dx) -> sy*3+sx into the OIHW
-// (.,.,3,3) master.  The stream nets of the H / I stacks run on the transposed (and, for I, then W-flipped) image
-// (reference feed_forward.py:236-256); with centred taps the transposed image is served by the transposed filter and
-// the flipped one by sx = 2 - dy (tests/test_gpu_ksize3.py pins all three against nn.Conv2d on the transformed image).
-__host__ __device__ static inline int master_tap9(int t, int variant)
-{
-    const int dy = t / 3, dx = t - 3 * (t / 3);
-    if (variant == 0) return dy * 3 + dx;         // identity
-    if (variant == 1) return dx * 3 + dy;         // transpose
-    return dx * 3 + (2 - dy);                     // transpose, then flip along W of the transposed image
+    const int dy = KS == 2 ? t >> 1 : t / KS, dx = t - KS * dy;   // (t >= 0; the shift spares 2x2 a signed division)
+    if (variant == 0) return dy * KS + dx;        // identity
+    if (variant == 1) return dx * KS + dy;        // transpose
+    return dx * KS + (KS - 1 - dy);               // transpose, then flip (2x2: along kernel-H; 3x3: along W of the transposed image)
 }
 
 // Running maxima in device memory: fire-and-forget atomic max -- no read of the slot, nothing to wait for.

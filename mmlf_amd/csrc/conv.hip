@@ -1,7 +1,8 @@
-// conv.hip -- MFMA implicit-GEMM kernels for the k=2 convolutions of the EPI-stack CNN, forward and data gradient, on the
-// padded NHWC grid (the weight + bias gradient: wgrad.hip; shared device helpers: conv_device.h).  gfx950 only.
-// Arithmetic paths with the same interfaces: exact-f32 MFMA (conv4tap_kernel) and the split paths at f32 accuracy
-// (conv4tap_x6s_kernel, conv4tap_rs_kernel: bf16x6 / f16x3).
+// conv.hip -- MFMA implicit-GEMM kernels for the k=2 and k=3 convolutions of the EPI-stack CNN, forward and data gradient,
+// on the padded NHWC grid (the weight + bias gradient: wgrad.hip; shared device helpers: conv_device.h).  gfx950 only.
+// Arithmetic paths with the same interfaces: exact-f32 MFMA (conv_f32_taps<KS, NT>, the one body behind conv4tap_kernel for
+// k=2 and conv9tap_kernel for k=3) and, for k=2, the split paths at f32 accuracy (conv4tap_x6s_kernel, conv4tap_rs_kernel:
+// bf16x6 / f16x3).
 //
 // Arithmetic replaced: nn.Conv2d(k=2, pad 1|0) forward / backward as used by
 // reference mmlf/model/feed_forward.py:123,125 (autograd via mmlf/train/cli.py:257).
@@ -29,26 +30,29 @@ extern "C" int mmlf_debug_oob_counts(unsigned long long *host8, int reset)
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// filter packing: OIHW master -> [chunk][tap][kh][NP][4] with k = 8*chunk + 4*kh + s
+// filter packing, exact f32: OIHW master (Cout, Cin, KS, KS) -> [chunk][tap(KS*KS)][kh][NP][4] with k = 8*chunk + 4*kh + s.
+// dgrad = 1 packs the data gradient's filter: taps rotated by 180 degrees, Cin / Cout swapped.
 // ---------------------------------------------------------------------------------------------
-__global__ void pack_filter_kernel(const float *__restrict__ w, float *__restrict__ out, int Cout, int Cin,
-                                   int variant, int dgrad, int nchunk, int NP)
+template <int KS>
+__global__ void pack_filter_f32_kernel(const float *__restrict__ w, float *__restrict__ out, int Cout, int Cin,
+                                       int variant, int dgrad, int nchunk, int NP)
 {
-    const long long total = (long long)nchunk * 4 * 2 * NP * 4;
+    constexpr int TAPS = KS * KS;
+    const long long total = (long long)nchunk * TAPS * 2 * NP * 4;
     for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
         int s = idx & 3;
         long long r = idx >> 2;
         int n = r % NP; r /= NP;
         int kh = r & 1; r >>= 1;
-        int t = r & 3; r >>= 2;
+        int t = r % TAPS; r /= TAPS;
         int c = (int)r;
         int k = 8 * c + 4 * kh + s;
         int ci, co, tsrc;
         if (!dgrad) { ci = k; co = n; tsrc = t; }
-        else { co = k; ci = n; tsrc = 3 - t; }
+        else { co = k; ci = n; tsrc = TAPS - 1 - t; }
         float v = 0.f;
-        if (ci < Cin && co < Cout) v = w[((size_t)co * Cin + ci) * 4 + master_tap(tsrc, variant)];
+        if (ci < Cin && co < Cout) v = w[((size_t)co * Cin + ci) * TAPS + master_tap<KS>(tsrc, variant)];
         out[idx] = v;
     }
 }
@@ -174,7 +178,7 @@ __device__ __forceinline__ void pack_filter_h2_column(const float *__restrict__ 
     if (tid == 0) unscale[n] = 1.f / sc;
     for (int e = tid; e < 4 * nchunk; e += 256) {
         const int c = e >> 2, t = e & 3;
-        const int tap = master_tap(dgrad ? 3 - t : t, variant);
+        const int tap = master_tap<2>(dgrad ? 3 - t : t, variant);
         unsigned short h[8], l[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -237,7 +241,7 @@ __global__ void pack_filter_split_kernel(const float *__restrict__ w, unsigned s
         if (!dgrad) { ci = k; co = n; tsrc = t; }
         else { co = k; ci = n; tsrc = 3 - t; }
         float v = 0.f;
-        if (ci < Cin && co < Cout) v = w[((size_t)co * Cin + ci) * 4 + master_tap(tsrc, variant)];
+        if (ci < Cin && co < Cout) v = w[((size_t)co * Cin + ci) * 4 + master_tap<2>(tsrc, variant)];
         unsigned p[3];
         split3(v, p[0], p[1], p[2]);
         for (int pl = 0; pl < 3; ++pl) {
@@ -1097,28 +1101,47 @@ __global__ __launch_bounds__(512, 2) void conv4tap_rs_kernel(ConvArgs a, int ngr
     }
 }
 
+// Exact-f32 forward / data-gradient kernels of both filter sizes: one body on KS = 2 (conv4tap_kernel, taps
+// {0, 1, P, P+1}) or 3 (conv9tap_kernel, taps dy*P + dx with dy, dx in {0, 1, 2}).
 // 512 threads = 8 waves; tile = 256 positions x NT*32 output channels; wave w owns positions
 // [32w, 32w+32) x all channels (NT accumulator tiles of 32x32).  K is walked in chunks of 8 input
-// channels x 4 taps, double-buffered in LDS and filled by LDS-DMA (global_load_lds_dwordx4: no
+// channels x KS*KS taps, double-buffered in LDS and filled by LDS-DMA (global_load_lds_dwordx4: no
 // staging registers; the copy of chunk c+1 is in flight while chunk c is multiplied):
-//   A (activations): [seg(2)][kh(2)][320] float4  -- seg 0 = positions Q0.., seg 1 = Q0+P..
-//   B (weights)    : [tap(4)][kh(2)][NP]  float4
+//   A (activations): [dy(KS)][kh(2)][320] float4  -- rows dy of the window, positions Q0 + dy*P + 0 .. 255 + KS-1
+//   B (weights)    : [tap(KS*KS)][kh(2)][NP] float4
 // One DMA wave-instruction ("piece") writes 64 consecutive float4 slots (1 KiB); its per-lane SOURCE
 // address does the gather (A: one position per lane; B: linear).  A lane (i = lane&31, kh = lane>>5)
 // reads ONE float4 = channels 4kh..4kh+3 of its position (A) or of its output channel (B): four K=2
 // MFMA steps pairing channel s of half 0 with 4+s of half 1.
-template <int NT>
-__global__ __launch_bounds__(512) void conv4tap_kernel(ConvArgs a)
+// Column blocks: the workgroup computes block `cb` of `ncb` blocks of NP columns of a filter packed np_total = ncb*NP
+// columns wide (blockIdx.x = tile*ncb + cb, so the column blocks of a tile run side by side and share its activation
+// window in L2).  The 2x2 launch has one block.  LDS budget of 3x3: 9 taps of B at 288 columns plus the 3-row window,
+// double-buffered, would be 227 KB (160 KiB per CU), so the columns per workgroup are bounded instead: NT <= 4 (<= 132 KiB
+// double-buffered), 288 columns as three blocks of 96.  Single-buffering B would keep 288 columns per workgroup but expose
+// the weight DMA once per chunk.
+template <int KS, int NT>
+struct ConvF32Lds {                                 // LDS layout of one pipeline buffer, in float4 (body and launcher)
+    static constexpr int A_STRIDE = 320;            // slots per (dy, kh) array: 5 DMA pieces (256 + KS - 1 used)
+    static constexpr int A_F4 = 2 * KS * A_STRIDE;
+    static constexpr int B_F4 = KS * KS * 2 * NT * 32;
+    static constexpr int BUF_F4 = A_F4 + B_F4;
+    static constexpr size_t BYTES = 2 * BUF_F4 * sizeof(float4);
+    static_assert(BYTES <= 160 * 1024, "exact-f32 convolution kernel: LDS per CU");
+};
+
+template <int KS, int NT>
+__device__ __forceinline__ void conv_f32_taps(const ConvArgs &a, const int ncb, const int np_total)
 {
+    using L = ConvF32Lds<KS, NT>;
+    constexpr int TAPS = KS * KS;
+    constexpr int WIN = 256 + KS - 1;           // positions of a window row
     constexpr int NP = NT * 32;
-    constexpr int A_STRIDE = 320;               // float4 slots per (seg, kh) array: 5 DMA pieces
-    constexpr int A_F4 = 4 * A_STRIDE;
-    constexpr int B_F4 = 4 * 2 * NP;
-    constexpr int BUF_F4 = A_F4 + B_F4;
-    constexpr int N_A = 20;                     // DMA pieces for A per chunk
+    constexpr int A_STRIDE = L::A_STRIDE, A_F4 = L::A_F4, B_F4 = L::B_F4, BUF_F4 = L::BUF_F4;
+    constexpr int N_A = 10 * KS;                // DMA pieces for A per chunk
     constexpr int N_PIECES = N_A + B_F4 / 64;   // + B pieces
     constexpr int PER_WAVE = (N_PIECES + 7) / 8;
-    static_assert(PER_WAVE <= 8, "piece schedule covers k = t and t + 4");
+    static_assert(B_F4 % 64 == 0 && PER_WAVE <= (KS == 2 ? 2 : 1) * TAPS,
+                  "piece schedule: piece k of a wave is issued at tap k (2x2: k = t and t + 4)");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4 *lds = reinterpret_cast<float4 *>(smem);
 
@@ -1126,7 +1149,8 @@ __global__ __launch_bounds__(512) void conv4tap_kernel(ConvArgs a)
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, kh = lane >> 5;
-    const long long Q0 = (long long)blockIdx.x * MMLF_TILE;
+    const int tile = blockIdx.x / ncb, cb = blockIdx.x - tile * ncb;
+    const long long Q0 = (long long)tile * MMLF_TILE;
 
     f32x16 acc[NT];
 #pragma unroll
@@ -1143,17 +1167,20 @@ __global__ __launch_bounds__(512) void conv4tap_kernel(ConvArgs a)
     for (int k = 0; k < PER_WAVE; ++k) {
         const int j = w + 8 * k;
         if (j < N_A) {
-            const int arr = j / 5, blk = j - 5 * arr;           // arr = seg*2 + kh
+            const int arr = j / 5, blk = j - 5 * arr;           // arr = dy*2 + kh
             int p = 64 * blk + lane;
-            p = p < 256 ? p : 256;                               // lanes past the tile re-read position 256
+            p = p < WIN ? p : WIN - 1;                           // lanes past the window re-read its last position
             src[k] = a.in + (size_t)(Q0 + (arr >> 1) * a.P + p) * a.cs_in + 4 * (arr & 1);
             dst_f4[k] = arr * A_STRIDE + 64 * blk;
             step[k] = 8;
         } else {
             const int b = (j < N_PIECES ? j : N_PIECES - 1) - N_A;
-            src[k] = a.wp + (size_t)(64 * b + lane) * 4;
+            const int s = 64 * b + lane, tk = s / NP;           // tk = tap*2 + kh: the row of the packed chunk
+            // column cb*NP + (s - tk*NP) of row tk, written so that one column block (np_total == NP, cb == 0) is the
+            // linear s without a division
+            src[k] = a.wp + (size_t)(s + tk * (np_total - NP) + cb * NP) * 4;
             dst_f4[k] = A_F4 + 64 * b;
-            step[k] = B_F4 * 4;
+            step[k] = TAPS * 2 * np_total * 4;
         }
     }
     const unsigned lds_base = (unsigned)(size_t)(lds_void_t *)smem;
@@ -1184,31 +1211,33 @@ __global__ __launch_bounds__(512) void conv4tap_kernel(ConvArgs a)
         const float4 *base = lds + buf * BUF_F4;
         const float4 *ap = base + kh * A_STRIDE + 32 * w + i;
         const float4 *bp = base + A_F4 + kh * NP + i;
-        // Software pipeline over the 4 taps: ALL fragment reads of tap t+1 are issued, then the 4*NT
+        // Software pipeline over the taps: ALL fragment reads of tap t+1 are issued, then the 4*NT
         // MFMAs of tap t run back to back while those reads land (sched_barrier pins the regions;
         // left alone, hipcc sinks each read to just before its first use).  The DMA pieces of chunk
-        // c+1 are spread over the taps, and the two waves that share a SIMD (w, w+4) issue theirs at
+        // c+1 are spread over the taps (a wave's piece k at tap k; 2x2 has fewer taps than a wave has
+        // pieces: k = t and t + 4), and the two waves that share a SIMD (w, w+4) issue theirs at
         // different points of the MFMA stream.  MFMAs stay accumulator-major (4 dependent K=2 steps
         // per accumulator): measured faster here than the independent order.
         float4 a_cur = ap[0], b_cur[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) b_cur[nt] = bp[32 * nt];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
+        for (int t = 0; t < TAPS; ++t) {
             float4 a_nxt = a_cur, b_nxt[NT];
-            if (t < 3) {
-                a_nxt = ap[((t + 1) >> 1) * 2 * A_STRIDE + ((t + 1) & 1)];
+            if (t < TAPS - 1) {
+                const int dy = (t + 1) / KS, dx = (t + 1) - KS * dy;
+                a_nxt = ap[dy * 2 * A_STRIDE + dx];
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) b_nxt[nt] = bp[(t + 1) * 2 * NP + 32 * nt];
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (more && w < 4) { CONV_DMA_PIECE(c + 1, buf ^ 1, t); CONV_DMA_PIECE(c + 1, buf ^ 1, t + 4); }
+            if (more && w < 4) { CONV_DMA_PIECE(c + 1, buf ^ 1, t); if (KS == 2) CONV_DMA_PIECE(c + 1, buf ^ 1, t + TAPS); }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 if (nt == NT / 2) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if (more && w >= 4) { CONV_DMA_PIECE(c + 1, buf ^ 1, t); CONV_DMA_PIECE(c + 1, buf ^ 1, t + 4); }
+                    if (more && w >= 4) { CONV_DMA_PIECE(c + 1, buf ^ 1, t); if (KS == 2) CONV_DMA_PIECE(c + 1, buf ^ 1, t + TAPS); }
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.x, b_cur[nt].x, acc[nt], 0, 0, 0);
@@ -1217,7 +1246,7 @@ __global__ __launch_bounds__(512) void conv4tap_kernel(ConvArgs a)
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.w, b_cur[nt].w, acc[nt], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (t < 3) {
+            if (t < TAPS - 1) {
                 a_cur = a_nxt;
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) b_cur[nt] = b_nxt[nt];
@@ -1229,7 +1258,28 @@ __global__ __launch_bounds__(512) void conv4tap_kernel(ConvArgs a)
 #undef CONV_DMA_PIECE
 #undef CONV_DMA_WAIT
 
-    conv_epilogue<NT>(a, acc, Q0, w, i, kh);
+    // this column block's slice of the output channels: the shared epilogue on shifted pointers
+    ConvArgs e = a;
+    const int c0 = cb * NP;
+    e.out = a.out + c0;
+    e.out_bytes = a.out_bytes - 4ll * c0;
+    e.bias = a.bias ? a.bias + c0 : nullptr;
+    if (a.ref) { e.ref = a.ref + c0; e.ref_bytes = a.ref_bytes - 4ll * c0; }
+    e.n_store = a.n_store - c0;
+    e.n_true = a.n_true - c0;
+    conv_epilogue<NT>(e, acc, Q0, w, i, kh);
+}
+
+template <int NT>
+__global__ __launch_bounds__(512) void conv4tap_kernel(ConvArgs a)
+{
+    conv_f32_taps<2, NT>(a, 1, NT * 32);
+}
+
+template <int NT>
+__global__ __launch_bounds__(512) void conv9tap_kernel(ConvArgs a, int ncb, int np_total)
+{
+    conv_f32_taps<3, NT>(a, ncb, np_total);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1237,36 +1287,46 @@ __global__ __launch_bounds__(512) void conv4tap_kernel(ConvArgs a)
 // ---------------------------------------------------------------------------------------------
 extern "C" int mmlf_conv_cus(void) { return device_cus(); }
 
-extern "C" int64_t mmlf_packed_filter_floats(int K, int N)
+// exact-f32 packed filters of both sizes (ks = 2 or 3): [chunk][tap(ks*ks)][kh(2)][NP][4] floats
+static int64_t packed_filter_f32_floats(int ks, int K, int N)
 {
     const int nt = pick_nt(N);
     if (nt < 0 || K <= 0) return -1;
-    return (int64_t)((K + 7) / 8) * 4 * 2 * (nt * 32) * 4;
+    return (int64_t)((K + 7) / 8) * ks * ks * 2 * (nt * 32) * 4;
 }
+
+static int pack_filter_f32(const char *who, int ks, const float *w, float *packed, int Cout, int Cin, int variant,
+                           int dgrad, void *stream)
+{
+    MMLF_CHECK_ARG(w && packed, "%s: null pointer", who);
+    MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "%s: bad variant %d", who, variant);
+    MMLF_CHECK_ARG(Cout > 0 && Cin > 0, "%s: bad channels %d x %d", who, Cout, Cin);
+    const int K = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;
+    const int nt = pick_nt(N);
+    MMLF_CHECK_ARG(nt > 0, "%s: N=%d not supported (max 288)", who, N);
+    const int nchunk = (K + 7) / 8, NP = nt * 32;
+    const long long total = (long long)nchunk * ks * ks * 2 * NP * 4;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(ks == 2 ? pack_filter_f32_kernel<2> : pack_filter_f32_kernel<3>, dim3(blocks), dim3(256), 0,
+                       (hipStream_t)stream, w, packed, Cout, Cin, variant, dgrad, nchunk, NP);
+    return mmlf_launch_status(who);
+}
+
+extern "C" int64_t mmlf_packed_filter_floats(int K, int N) { return packed_filter_f32_floats(2, K, N); }
 
 extern "C" int mmlf_pack_filter(const float *w, float *packed, int Cout, int Cin, int variant, int dgrad,
                                 void *stream)
 {
-    MMLF_CHECK_ARG(w && packed, "mmlf_pack_filter: null pointer");
-    MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_pack_filter: bad variant %d", variant);
-    const int K = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;
-    const int nt = pick_nt(N);
-    MMLF_CHECK_ARG(nt > 0, "mmlf_pack_filter: N=%d not supported (max 288)", N);
-    const int nchunk = (K + 7) / 8, NP = nt * 32;
-    const long long total = (long long)nchunk * 32 * NP;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pack_filter_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin,
-                       variant, dgrad, nchunk, NP);
-    return mmlf_launch_status("mmlf_pack_filter");
+    return pack_filter_f32("mmlf_pack_filter", 2, w, packed, Cout, Cin, variant, dgrad, stream);
 }
 
-// What the ABI's contract says the caller's buffers hold (bytes behind the pointers as passed).  `out` may be a channel
-// slice of a wider buffer (out = base + c_off with c_off + N_store <= cs_out): the bound below is what is left behind the
-// LARGEST such offset, so it never cuts a store the contract allows and never exceeds the allocation.
-static void conv_buffer_bytes(ConvArgs &a, const Grid &g)
+// What the ABI's contract says the caller's buffers hold (bytes behind the pointers as passed), alloc = the positions the
+// grid's allocation rule gives them.  `out` may be a channel slice of a wider buffer (out = base + c_off with c_off +
+// N_store <= cs_out): the bound below is what is left behind the LARGEST such offset, so it never cuts a store the
+// contract allows and never exceeds the allocation.
+static void conv_buffer_bytes(ConvArgs &a, const Grid &g, long long alloc)
 {
-    const long long alloc = grid_alloc_positions(g);
     a.out_bytes = (alloc * a.cs_out - (a.cs_out - a.n_store)) * 4;
     a.ref_bytes = a.ref ? alloc * a.cs_ref * 4 : 0;
     a.in_bytes = alloc * a.cs_in * 4;
@@ -1274,47 +1334,67 @@ static void conv_buffer_bytes(ConvArgs &a, const Grid &g)
     a.mask_words = g.NQpad / MMLF_TILE * 4096;
 }
 
-template <int NT>
-static int launch_conv(const ConvArgs &a, long long ntiles, hipStream_t st)
+// The argument checks and the ConvArgs fields that every forward / data-gradient entry point shares.  who = the entry
+// point as the caller named it, ks = filter size (window slack: taps reach (ks-1)(P+1) past a tile), np = packed columns
+// by the path's own rule (<= 0: N not supported).
+static int conv_common_args(const char *who, int ks, int np, ConvArgs &a, Grid &g, const float *in, int cs_in, int K,
+                            const void *packed, const float *bias, int N, float *out, int cs_out, int N_store,
+                            int out_shift, int vh, int vw, int B, int H, int W, int relu, const float *relu_ref, int cs_ref)
 {
-    constexpr size_t lds = 2 * (4 * 320 + 4 * 2 * NT * 32) * sizeof(float4);
+    MMLF_CHECK_ARG(in && packed && out, "%s: null pointer", who);
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+    MMLF_CHECK_ARG(cs_in > 0 && cs_in % 8 == 0, "%s: cs_in=%d must be a multiple of 8", who, cs_in);
+    MMLF_CHECK_ARG(K > 0 && (K + 7) / 8 * 8 == cs_in, "%s: K=%d does not match cs_in=%d", who, K, cs_in);
+    MMLF_CHECK_ARG(np > 0, "%s: N=%d not supported (max 288)", who, N);
+    MMLF_CHECK_ARG(N_store > 0 && N_store <= cs_out && N_store <= np, "%s: N_store=%d vs cs_out=%d NP=%d", who,
+                   N_store, cs_out, np);
+    g = make_grid(B, H, W);
+    MMLF_CHECK_ARG(out_shift >= 0 && out_shift <= g.P + 1, "%s: out_shift=%d", who, out_shift);
+    MMLF_CHECK_ARG(!relu_ref || cs_ref >= N_store, "%s: cs_ref=%d < N_store", who, cs_ref);
+    MMLF_CHECK_ARG(g.NQpad + (ks - 1) * g.P + 64 < (1ll << 31), "%s: batch x image too large for 32-bit grid positions", who);
+    a = {};
+    a.in = in; a.wp = reinterpret_cast<const float *>(packed); a.bias = bias; a.out = out; a.ref = relu_ref;
+    a.NQ = g.NQ; a.cs_in = cs_in; a.nchunk = cs_in / 8; a.cs_out = cs_out; a.n_store = N_store; a.n_true = N;
+    a.out_shift = out_shift; a.vh = vh; a.vw = vw; a.P = g.P; a.G = g.G; a.R = g.R; a.relu = relu; a.cs_ref = cs_ref;
+    a.divP = make_magic((unsigned)g.P); a.divR = make_magic((unsigned)g.R);
+    conv_buffer_bytes(a, g, ks == 3 ? grid_alloc_positions_k3(g) : grid_alloc_positions(g));
+    return 0;
+}
+
+// ncb column blocks of NT*32 columns per tile (2x2: always one)
+template <int KS, int NT>
+static int launch_conv_f32(const ConvArgs &a, long long ntiles, int ncb, hipStream_t st)
+{
+    constexpr const char *who = KS == 2 ? "mmlf_conv2x2" : "mmlf_conv3x3";
+    constexpr size_t lds = ConvF32Lds<KS, NT>::BYTES;
     static PerDeviceOnce attr_once;
-    if (attr_once.run([] { return mmlf_allow_lds(reinterpret_cast<const void *>(conv4tap_kernel<NT>), lds, "mmlf_conv2x2"); }))
-        return 1;
-    hipLaunchKernelGGL(conv4tap_kernel<NT>, dim3((unsigned)ntiles), dim3(512), lds, st, a);
-    return mmlf_launch_status("mmlf_conv2x2");
+    if constexpr (KS == 2) {
+        if (attr_once.run([] { return mmlf_allow_lds(reinterpret_cast<const void *>(conv4tap_kernel<NT>), lds, who); })) return 1;
+        hipLaunchKernelGGL(conv4tap_kernel<NT>, dim3((unsigned)ntiles), dim3(512), lds, st, a);
+    } else {
+        if (attr_once.run([] { return mmlf_allow_lds(reinterpret_cast<const void *>(conv9tap_kernel<NT>), lds, who); })) return 1;
+        hipLaunchKernelGGL(conv9tap_kernel<NT>, dim3((unsigned)(ntiles * ncb)), dim3(512), lds, st, a, ncb, ncb * NT * 32);
+    }
+    return mmlf_launch_status(who);
 }
 
 extern "C" int mmlf_conv2x2(const float *in, int cs_in, int K, const float *packed, const float *bias, int N,
                             float *out, int cs_out, int N_store, int out_shift, int vh, int vw, int B, int H,
                             int W, int relu, const float *relu_ref, int cs_ref, void *stream)
 {
-    MMLF_CHECK_ARG(in && packed && out, "mmlf_conv2x2: null pointer");
-    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_conv2x2: bad shape B=%d H=%d W=%d", B, H, W);
-    MMLF_CHECK_ARG(cs_in > 0 && cs_in % 8 == 0, "mmlf_conv2x2: cs_in=%d must be a multiple of 8", cs_in);
-    MMLF_CHECK_ARG(K > 0 && (K + 7) / 8 * 8 == cs_in, "mmlf_conv2x2: K=%d does not match cs_in=%d", K, cs_in);
     const int nt = pick_nt(N);
-    MMLF_CHECK_ARG(nt > 0, "mmlf_conv2x2: N=%d not supported (max 288)", N);
-    MMLF_CHECK_ARG(N_store > 0 && N_store <= cs_out && N_store <= nt * 32,
-                   "mmlf_conv2x2: N_store=%d vs cs_out=%d NP=%d", N_store, cs_out, nt * 32);
-    Grid g = make_grid(B, H, W);
-    MMLF_CHECK_ARG(out_shift >= 0 && out_shift <= g.P + 1, "mmlf_conv2x2: out_shift=%d", out_shift);
-    MMLF_CHECK_ARG(!relu_ref || cs_ref >= N_store, "mmlf_conv2x2: cs_ref=%d < N_store", cs_ref);
-    ConvArgs a = {};
-    a.in = in; a.wp = packed; a.bias = bias; a.out = out; a.ref = relu_ref;
-    a.NQ = g.NQ; a.cs_in = cs_in; a.nchunk = cs_in / 8; a.cs_out = cs_out; a.n_store = N_store; a.n_true = N;
-    a.out_shift = out_shift; a.vh = vh; a.vw = vw; a.P = g.P; a.G = g.G; a.relu = relu; a.cs_ref = cs_ref;
-    a.divP = make_magic((unsigned)g.P); a.divR = make_magic((unsigned)g.R); a.R = g.R;
-    a.relu_mask_out = nullptr; a.relu_mask_in = nullptr;
-    conv_buffer_bytes(a, g);
-    MMLF_CHECK_ARG(g.NQpad + g.P + 64 < (1ll << 31), "mmlf_conv2x2: batch x image too large for 32-bit grid positions");
+    ConvArgs a;
+    Grid g;
+    if (conv_common_args("mmlf_conv2x2", 2, nt * 32, a, g, in, cs_in, K, packed, bias, N, out, cs_out, N_store, out_shift, vh,
+                         vw, B, H, W, relu, relu_ref, cs_ref))
+        return 1;
     const long long ntiles = g.NQpad / MMLF_TILE;
     hipStream_t st = (hipStream_t)stream;
     switch (nt) {
-    case 1: return launch_conv<1>(a, ntiles, st);
-    case 3: return launch_conv<3>(a, ntiles, st);
-    case 4: return launch_conv<4>(a, ntiles, st);
-    default: return launch_conv<9>(a, ntiles, st);
+    case 1: return launch_conv_f32<2, 1>(a, ntiles, 1, st);
+    case 3: return launch_conv_f32<2, 3>(a, ntiles, 1, st);
+    case 4: return launch_conv_f32<2, 4>(a, ntiles, 1, st);
+    default: return launch_conv_f32<2, 9>(a, ntiles, 1, st);
     }
 }
 
@@ -1515,34 +1595,22 @@ static int conv_split_impl(const char *who, int planes, const float *in, int cs_
                            const float *in_amax, float *out_amax, double *bn_partial, void *stream,
                            unsigned *relu_mask_out = nullptr, const unsigned *relu_mask_in = nullptr)
 {
-    MMLF_CHECK_ARG(in && packed && out, "%s: null pointer", who);
-    MMLF_CHECK_ARG(!(relu_ref && relu_mask_in), "%s: relu_ref and relu_mask_in are alternatives", who);
-    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
-    MMLF_CHECK_ARG(cs_in > 0 && cs_in % 8 == 0, "%s: cs_in=%d must be a multiple of 8", who, cs_in);
-    MMLF_CHECK_ARG(K > 0 && (K + 7) / 8 * 8 == cs_in, "%s: K=%d does not match cs_in=%d", who, K, cs_in);
     const int np = x6_np(N);
-    MMLF_CHECK_ARG(np > 0, "%s: N=%d not supported (max 288)", who, N);
-    MMLF_CHECK_ARG(N_store > 0 && N_store <= cs_out && N_store <= np, "%s: N_store=%d vs cs_out=%d NP=%d", who,
-                   N_store, cs_out, np);
-    Grid g = make_grid(B, H, W);
-    MMLF_CHECK_ARG(out_shift >= 0 && out_shift <= g.P + 1, "%s: out_shift=%d", who, out_shift);
-    MMLF_CHECK_ARG(!relu_ref || cs_ref >= N_store, "%s: cs_ref=%d < N_store", who, cs_ref);
+    ConvArgs a;
+    Grid g;
+    if (conv_common_args(who, 2, np, a, g, in, cs_in, K, packed, bias, N, out, cs_out, N_store, out_shift, vh, vw, B, H, W, relu,
+                         relu_ref, cs_ref))
+        return 1;
+    MMLF_CHECK_ARG(!(relu_ref && relu_mask_in), "%s: relu_ref and relu_mask_in are alternatives", who);
     MMLF_CHECK_ARG((long long)cs_in * 4 * 64 < (1ll << 31), "%s: cs_in too large", who);
     MMLF_CHECK_ARG(planes == 3 || in_amax, "%s: the f16 split needs the input's max |x|", who);
-    ConvArgs a = {};
-    a.in = in; a.wp = reinterpret_cast<const float *>(packed); a.bias = bias; a.out = out; a.ref = relu_ref;
-    a.NQ = g.NQ; a.cs_in = cs_in; a.nchunk = cs_in / 8; a.cs_out = cs_out; a.n_store = N_store; a.n_true = N;
-    a.out_shift = out_shift; a.vh = vh; a.vw = vw; a.P = g.P; a.G = g.G; a.relu = relu; a.cs_ref = cs_ref;
+    MMLF_CHECK_ARG(!bn_partial || (planes == 2 && N_store >= N), "%s: BatchNorm statistics need the f16 split path", who);
     a.in_amax = in_amax; a.out_amax = out_amax; a.bn_partial = bn_partial;
     a.relu_mask_out = relu_mask_out; a.relu_mask_in = relu_mask_in;
-    conv_buffer_bytes(a, g);
-    MMLF_CHECK_ARG(!bn_partial || (planes == 2 && N_store >= N), "%s: BatchNorm statistics need the f16 split path", who);
     // the f16-packed filter ends with its columns' unscale factors
     a.w_unscale = planes == 2 ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(packed) +
                                                                   (size_t)(cs_in / 8) * 8 * np * 16)
                               : nullptr;
-    a.divP = make_magic((unsigned)g.P); a.divR = make_magic((unsigned)g.R); a.R = g.R;
-    MMLF_CHECK_ARG(g.NQpad + g.P + 64 < (1ll << 31), "%s: batch x image too large for 32-bit grid positions", who);
     a.nw = conv_sixteen_waves(planes, np, g) ? 16 : 8;
     const int tile = 32 * a.nw;
     if (g.P + tile + 1 <= 640) {   // one contiguous window of tile + 1 + P positions
@@ -1668,8 +1736,8 @@ __global__ __launch_bounds__(256) void thin_rowdot_kernel(ThinArgs a)
                 float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (c < a.C && o < a.N) {
                     const float *wp = a.w + ((size_t)o * a.C + c) * 4;
-                    w4 = make_float4(wp[master_tap(0, a.variant)], wp[master_tap(1, a.variant)], wp[master_tap(2, a.variant)],
-                                     wp[master_tap(3, a.variant)]);
+                    w4 = make_float4(wp[master_tap<2>(0, a.variant)], wp[master_tap<2>(1, a.variant)], wp[master_tap<2>(2, a.variant)],
+                                     wp[master_tap<2>(3, a.variant)]);
                 }
                 wt[wv][lane & 31][o] = w4;
             }
@@ -1836,168 +1904,9 @@ extern "C" int mmlf_audit_conv_h2(int cs_in, int K, int N, int cs_out, int N_sto
 // 3x3 ("same", pad 1) convolution, exact-f32 MFMA: nn.Conv2d(k=3, padding=1) forward and data gradient
 // (reference feed_forward.py:123,125 with --model_ksize 3).  Nine taps at q + dy*P + dx, dy, dx in {0, 1, 2}; the
 // output goes to q + P + 1 (extent (H, W) at grid offset (1, 1)); the data gradient is the same correlation with the
-// taps rotated by 180 degrees and Cin / Cout swapped (pack_filter9_kernel, dgrad = 1).
+// taps rotated by 180 degrees and Cin / Cout swapped (pack_filter_f32_kernel<3>, dgrad = 1).  The kernel is
+// conv9tap_kernel = conv_f32_taps<3, NT> above; here its launch shape and entry points.
 // ---------------------------------------------------------------------------------------------
-// OIHW (Cout, Cin, 3, 3) -> [chunk][tap(9)][kh(2)][NP][4] with k = 8*chunk + 4*kh + s
-__global__ void pack_filter9_kernel(const float *__restrict__ w, float *__restrict__ out, int Cout, int Cin,
-                                    int variant, int dgrad, int nchunk, int NP)
-{
-    const long long total = (long long)nchunk * 9 * 2 * NP * 4;
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        int s = idx & 3;
-        long long r = idx >> 2;
-        int n = r % NP; r /= NP;
-        int kh = r & 1; r >>= 1;
-        int t = r % 9; r /= 9;
-        int c = (int)r;
-        int k = 8 * c + 4 * kh + s;
-        int ci, co, tsrc;
-        if (!dgrad) { ci = k; co = n; tsrc = t; }
-        else { co = k; ci = n; tsrc = 8 - t; }
-        float v = 0.f;
-        if (ci < Cin && co < Cout) v = w[((size_t)co * Cin + ci) * 9 + master_tap9(tsrc, variant)];
-        out[idx] = v;
-    }
-}
-
-// Tile of 256 positions (8 waves x 32) x NT*32 output channels; column block `cb` of `ncb` (blockIdx.x = tile*ncb + cb, so
-// the column blocks of a tile run side by side and share its activation window in L2).  Per 8-channel chunk:
-//   A (activations): [dy(3)][kh(2)][320] float4 -- rows dy of the window, positions Q0 + dy*P + 0..257
-//   B (weights)    : [tap(9)][kh(2)][NP] float4
-// LDS budget: 9 taps of B at 288 columns plus the 3-row window, double-buffered, would be 227 KB (160 KiB per CU), so the
-// columns per workgroup are bounded instead: NT <= 4 (<= 132 KiB double-buffered), 288 columns as three blocks of 96.
-// Single-buffering B would keep 288 columns per workgroup but expose the weight DMA once per chunk.
-template <int NT>
-__global__ __launch_bounds__(512) void conv9tap_kernel(ConvArgs a, int ncb, int np_total)
-{
-    constexpr int NP = NT * 32;
-    constexpr int A_STRIDE = 320;               // float4 slots per (dy, kh) array: 5 DMA pieces (258 used)
-    constexpr int A_F4 = 6 * A_STRIDE;
-    constexpr int B_F4 = 9 * 2 * NP;
-    constexpr int BUF_F4 = A_F4 + B_F4;
-    constexpr int N_A = 30;                     // DMA pieces for A per chunk
-    constexpr int N_PIECES = N_A + B_F4 / 64;   // + B pieces
-    constexpr int PER_WAVE = (N_PIECES + 7) / 8;
-    static_assert(B_F4 % 64 == 0 && PER_WAVE <= 9, "piece schedule: piece k of a wave is issued at tap k");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4 *lds = reinterpret_cast<float4 *>(smem);
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i = lane & 31, kh = lane >> 5;
-    const int tile = blockIdx.x / ncb, cb = blockIdx.x - tile * ncb;
-    const long long Q0 = (long long)tile * MMLF_TILE;
-
-    f32x16 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-
-    // per-lane DMA sources of this wave's pieces j = w, w+8, ...; chunk c adds c*step floats
-    const float *src[PER_WAVE];
-    int dst_f4[PER_WAVE];
-    int step[PER_WAVE];
-#pragma unroll
-    for (int k = 0; k < PER_WAVE; ++k) {
-        const int j = w + 8 * k;
-        if (j < N_A) {
-            const int arr = j / 5, blk = j - 5 * arr;           // arr = dy*2 + kh
-            int p = 64 * blk + lane;
-            p = p < 258 ? p : 257;                               // lanes past the window re-read its last position
-            src[k] = a.in + (size_t)(Q0 + (arr >> 1) * a.P + p) * a.cs_in + 4 * (arr & 1);
-            dst_f4[k] = arr * A_STRIDE + 64 * blk;
-            step[k] = 8;
-        } else {
-            const int b = (j < N_PIECES ? j : N_PIECES - 1) - N_A;
-            const int s = 64 * b + lane, tk = s / NP, n = s - tk * NP;   // tk = tap*2 + kh
-            src[k] = a.wp + ((size_t)tk * np_total + cb * NP + n) * 4;
-            dst_f4[k] = A_F4 + 64 * b;
-            step[k] = 18 * np_total * 4;
-        }
-    }
-    const unsigned lds_base = (unsigned)(size_t)(lds_void_t *)smem;
-
-#define CONV9_DMA_PIECE(c, buf, k)                                                                \
-    do {                                                                                          \
-        if ((k) < PER_WAVE && w + 8 * (k) < N_PIECES) {                                           \
-            const float *g_ = src[k] + (size_t)(c) * step[k];                                     \
-            const unsigned d_ = lds_base + (unsigned)(((buf) * BUF_F4 + dst_f4[k]) * 16);         \
-            unsigned keep_;                                                                       \
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"                \
-                         "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"                   \
-                         : "=&s"(keep_) : "v"(g_), "s"(d_) : "memory");                          \
-        }                                                                                         \
-    } while (0)
-#define CONV9_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-
-#pragma unroll
-    for (int k = 0; k < PER_WAVE; ++k) CONV9_DMA_PIECE(0, 0, k);
-    CONV9_DMA_WAIT();
-    __syncthreads();
-
-    for (int c = 0; c < a.nchunk; ++c) {
-        const int buf = c & 1;
-        const bool more = c + 1 < a.nchunk;
-        const float4 *base = lds + buf * BUF_F4;
-        const float4 *ap = base + kh * A_STRIDE + 32 * w + i;
-        const float4 *bp = base + A_F4 + kh * NP + i;
-        // the same software pipeline as conv4tap_kernel, over 9 taps: the fragment reads of tap t+1 are issued, then the
-        // 4*NT MFMAs of tap t run while they land; the DMA pieces of chunk c+1 are spread over the taps (piece k at tap k)
-        float4 a_cur = ap[0], b_cur[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) b_cur[nt] = bp[32 * nt];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            float4 a_nxt = a_cur, b_nxt[NT];
-            if (t < 8) {
-                const int dy = (t + 1) / 3, dx = (t + 1) - 3 * ((t + 1) / 3);
-                a_nxt = ap[dy * 2 * A_STRIDE + dx];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) b_nxt[nt] = bp[(t + 1) * 2 * NP + 32 * nt];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (more && w < 4) CONV9_DMA_PIECE(c + 1, buf ^ 1, t);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                if (nt == NT / 2) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (more && w >= 4) CONV9_DMA_PIECE(c + 1, buf ^ 1, t);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.x, b_cur[nt].x, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.y, b_cur[nt].y, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.z, b_cur[nt].z, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur.w, b_cur[nt].w, acc[nt], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (t < 8) {
-                a_cur = a_nxt;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) b_cur[nt] = b_nxt[nt];
-            }
-        }
-        CONV9_DMA_WAIT();
-        __syncthreads();
-    }
-#undef CONV9_DMA_PIECE
-#undef CONV9_DMA_WAIT
-
-    // this column block's slice of the output channels: the shared epilogue on shifted pointers
-    ConvArgs e = a;
-    const int c0 = cb * NP;
-    e.out = a.out + c0;
-    e.out_bytes = a.out_bytes - 4ll * c0;
-    e.bias = a.bias ? a.bias + c0 : nullptr;
-    if (a.ref) { e.ref = a.ref + c0; e.ref_bytes = a.ref_bytes - 4ll * c0; }
-    e.n_store = a.n_store - c0;
-    e.n_true = a.n_true - c0;
-    conv_epilogue<NT>(e, acc, Q0, w, i, kh);
-}
-
 // 3x3 launch shape: NT 32-column tiles per workgroup, ncb column blocks
 static inline bool conv9_shape(int N, int *nt, int *ncb)
 {
@@ -2008,73 +1917,31 @@ static inline bool conv9_shape(int N, int *nt, int *ncb)
     return true;
 }
 
-extern "C" int64_t mmlf_packed_filter3x3_floats(int K, int N)
-{
-    const int nt = pick_nt(N);
-    if (nt < 0 || K <= 0) return -1;
-    return (int64_t)((K + 7) / 8) * 9 * 2 * (nt * 32) * 4;
-}
+extern "C" int64_t mmlf_packed_filter3x3_floats(int K, int N) { return packed_filter_f32_floats(3, K, N); }
 
 extern "C" int mmlf_pack_filter3x3(const float *w, float *packed, int Cout, int Cin, int variant, int dgrad, void *stream)
 {
-    MMLF_CHECK_ARG(w && packed, "mmlf_pack_filter3x3: null pointer");
-    MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_pack_filter3x3: bad variant %d", variant);
-    MMLF_CHECK_ARG(Cout > 0 && Cin > 0, "mmlf_pack_filter3x3: bad channels %d x %d", Cout, Cin);
-    const int K = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;
-    const int nt = pick_nt(N);
-    MMLF_CHECK_ARG(nt > 0, "mmlf_pack_filter3x3: N=%d not supported (max 288)", N);
-    const int nchunk = (K + 7) / 8, NP = nt * 32;
-    const long long total = (long long)nchunk * 9 * 2 * NP * 4;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pack_filter9_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin,
-                       variant, dgrad, nchunk, NP);
-    return mmlf_launch_status("mmlf_pack_filter3x3");
-}
-
-template <int NT>
-static int launch_conv9(const ConvArgs &a, long long ntiles, int ncb, int np_total, hipStream_t st)
-{
-    constexpr size_t lds = 2 * (6 * 320 + 9 * 2 * NT * 32) * sizeof(float4);
-    static_assert(lds <= 160 * 1024, "conv9tap_kernel: LDS per CU");
-    static PerDeviceOnce attr_once;
-    if (attr_once.run([] { return mmlf_allow_lds(reinterpret_cast<const void *>(conv9tap_kernel<NT>), lds, "mmlf_conv3x3"); }))
-        return 1;
-    hipLaunchKernelGGL(conv9tap_kernel<NT>, dim3((unsigned)(ntiles * ncb)), dim3(512), lds, st, a, ncb, np_total);
-    return mmlf_launch_status("mmlf_conv3x3");
+    return pack_filter_f32("mmlf_pack_filter3x3", 3, w, packed, Cout, Cin, variant, dgrad, stream);
 }
 
 extern "C" int mmlf_conv3x3(const float *in, int cs_in, int K, const float *packed, const float *bias, int N,
                             float *out, int cs_out, int N_store, int B, int H, int W, int relu, const float *relu_ref,
                             int cs_ref, void *stream)
 {
-    MMLF_CHECK_ARG(in && packed && out, "mmlf_conv3x3: null pointer");
-    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_conv3x3: bad shape B=%d H=%d W=%d", B, H, W);
-    MMLF_CHECK_ARG(cs_in > 0 && cs_in % 8 == 0, "mmlf_conv3x3: cs_in=%d must be a multiple of 8", cs_in);
-    MMLF_CHECK_ARG(K > 0 && (K + 7) / 8 * 8 == cs_in, "mmlf_conv3x3: K=%d does not match cs_in=%d", K, cs_in);
-    int nt, ncb;
-    MMLF_CHECK_ARG(conv9_shape(N, &nt, &ncb), "mmlf_conv3x3: N=%d not supported (max 288)", N);
-    MMLF_CHECK_ARG(N_store > 0 && N_store <= cs_out && N_store <= nt * ncb * 32,
-                   "mmlf_conv3x3: N_store=%d vs cs_out=%d NP=%d", N_store, cs_out, nt * ncb * 32);
-    MMLF_CHECK_ARG(!relu_ref || cs_ref >= N_store, "mmlf_conv3x3: cs_ref=%d < N_store", cs_ref);
-    const Grid g = make_grid(B, H, W);
-    MMLF_CHECK_ARG(g.NQpad + 2 * g.P + 64 < (1ll << 31), "mmlf_conv3x3: batch x image too large for 32-bit grid positions");
-    ConvArgs a = {};
-    a.in = in; a.wp = packed; a.bias = bias; a.out = out; a.ref = relu_ref;
-    a.NQ = g.NQ; a.cs_in = cs_in; a.nchunk = cs_in / 8; a.cs_out = cs_out; a.n_store = N_store; a.n_true = N;
-    a.out_shift = g.P + 1; a.vh = H; a.vw = W; a.P = g.P; a.G = g.G; a.relu = relu; a.cs_ref = cs_ref;
-    a.divP = make_magic((unsigned)g.P); a.divR = make_magic((unsigned)g.R); a.R = g.R;
-    const long long alloc = grid_alloc_positions_k3(g);
-    a.out_bytes = (alloc * cs_out - (cs_out - N_store)) * 4;
-    a.ref_bytes = relu_ref ? alloc * cs_ref * 4 : 0;
-    a.in_bytes = alloc * cs_in * 4;
+    int nt = -1, ncb = 1;
+    conv9_shape(N, &nt, &ncb);
+    ConvArgs a;
+    Grid g;
+    // the output goes to q + P + 1 (P = W + GRID_PAD), valid extent (H, W)
+    if (conv_common_args("mmlf_conv3x3", 3, nt * ncb * 32, a, g, in, cs_in, K, packed, bias, N, out, cs_out, N_store,
+                         W + GRID_PAD + 1, H, W, B, H, W, relu, relu_ref, cs_ref))
+        return 1;
     const long long ntiles = g.NQpad / MMLF_TILE;
-    const int np_total = nt * ncb * 32;
     hipStream_t st = (hipStream_t)stream;
     switch (nt) {
-    case 1: return launch_conv9<1>(a, ntiles, ncb, np_total, st);
-    case 3: return launch_conv9<3>(a, ntiles, ncb, np_total, st);
-    default: return launch_conv9<4>(a, ntiles, ncb, np_total, st);
+    case 1: return launch_conv_f32<3, 1>(a, ntiles, ncb, st);
+    case 3: return launch_conv_f32<3, 3>(a, ntiles, ncb, st);
+    default: return launch_conv_f32<3, 4>(a, ntiles, ncb, st);
     }
 }
 

@@ -1358,24 +1358,27 @@ extern "C" int mmlf_bn_coeffs_eval(const float *gamma, const float *beta, const 
     return mmlf_launch_status("mmlf_bn_coeffs_eval");
 }
 
+// BatchNorm folded into the convolution in front of it; taps = filter elements per (co, ci): 4 or 9
+static int fold_bn_eval(const char *who, int taps, const float *w_oihw, const float *bias, const float *scale,
+                        const float *shift, float *w_out, float *bias_out, int Cout, int Cin, void *stream)
+{
+    MMLF_CHECK_ARG(w_oihw && scale && shift && w_out && bias_out && Cout > 0 && Cin > 0, "%s: bad argument", who);
+    const long long total = (long long)Cout * Cin * taps;
+    hipLaunchKernelGGL(fold_bn_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, w_oihw, bias, scale,
+                       shift, w_out, bias_out, Cout, Cin * taps);
+    return mmlf_launch_status(who);
+}
+
 extern "C" int mmlf_fold_bn_eval(const float *w_oihw, const float *bias, const float *scale, const float *shift,
                                  float *w_out, float *bias_out, int Cout, int Cin, void *stream)
 {
-    MMLF_CHECK_ARG(w_oihw && scale && shift && w_out && bias_out && Cout > 0 && Cin > 0, "mmlf_fold_bn_eval: bad argument");
-    const long long total = (long long)Cout * Cin * 4;
-    hipLaunchKernelGGL(fold_bn_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, w_oihw, bias, scale,
-                       shift, w_out, bias_out, Cout, Cin * 4);
-    return mmlf_launch_status("mmlf_fold_bn_eval");
+    return fold_bn_eval("mmlf_fold_bn_eval", 4, w_oihw, bias, scale, shift, w_out, bias_out, Cout, Cin, stream);
 }
 
 extern "C" int mmlf_fold_bn_eval3x3(const float *w_oihw, const float *bias, const float *scale, const float *shift,
                                     float *w_out, float *bias_out, int Cout, int Cin, void *stream)
 {
-    MMLF_CHECK_ARG(w_oihw && scale && shift && w_out && bias_out && Cout > 0 && Cin > 0, "mmlf_fold_bn_eval3x3: bad argument");
-    const long long total = (long long)Cout * Cin * 9;
-    hipLaunchKernelGGL(fold_bn_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, w_oihw, bias, scale,
-                       shift, w_out, bias_out, Cout, Cin * 9);
-    return mmlf_launch_status("mmlf_fold_bn_eval3x3");
+    return fold_bn_eval("mmlf_fold_bn_eval3x3", 9, w_oihw, bias, scale, shift, w_out, bias_out, Cout, Cin, stream);
 }
 
 extern "C" int mmlf_bn_apply_relu(const float *z, int cs_z, int C, const float *scale, const float *shift, float *y,

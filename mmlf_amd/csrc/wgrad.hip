@@ -1,5 +1,6 @@
-// wgrad.hip -- weight + bias gradient of the k=2 convolutions on the padded NHWC grid (exact-f32 MFMA kernel and the
-// split-arithmetic kernels wgrad4tap_x6w / x6n), the thin (1-2 output channel) weight gradient, their C ABI entry points.
+// wgrad.hip -- weight + bias gradient of the k=2 and k=3 convolutions on the padded NHWC grid (exact-f32 MFMA:
+// wgrad_f32_taps<KS, NT>, the one body behind wgrad4tap_kernel and wgrad9tap_kernel; for k=2 also the split-arithmetic
+// kernels wgrad4tap_x6w / x6n), the thin (1-2 output channel) weight gradient, their C ABI entry points.
 // gfx950 only.  Arithmetic replaced: the weight / bias gradient of nn.Conv2d(k=2, pad 1|0), reference
 // mmlf/model/feed_forward.py:123,125 under autograd (mmlf/train/cli.py:257).
 #include "conv_device.h"
@@ -60,26 +61,46 @@ static inline unsigned wgrad_grid_blocks(int nslice, int nsplit)
 
 #define WG_KQ 32  // positions per chunk
 
-// 256 threads = 4 waves, wave t = tap t.  Block = (32-channel ci slice, position split).
+// Exact-f32 weight + bias gradient of both filter sizes: one body on KS = 2 (wgrad4tap_kernel) or 3 (wgrad9tap_kernel),
+//   gw[co][ci][tap] (+)= sum_q in[q + dy*P + dx][ci] * g[q + g_shift][co],  gb[co] (+)= sum_q g[q + g_shift][co].
 // MFMA rows = ci (A operand), cols = co (B operand), K = positions.  The first channel past Cin
 // is staged as 1.0 so that row Cin of tap 0 accumulates the bias gradient for free.
-template <int NT>
-__global__ __launch_bounds__(256, 2) void wgrad4tap_kernel(WgradArgs a)
+//  KS = 2: 256 threads = 4 waves, wave = tap (dy, dx); block = (32-channel ci slice, position split), both tap rows staged.
+//  KS = 3: one tap ROW per workgroup: 192 threads = 3 waves, wave = dx; block = (32-channel ci slice, dy, position
+//          split), so that nine accumulator sets of up to 9 x 16 registers never share a workgroup.  The gradient tile is
+//          staged once per (slice, dy) block; the three dy blocks of a slice read it from L2.
+// Partial sums: [nsplit][KS*KS][CIP][NP].
+template <int KS>
+struct WgradF32Shape {
+    static constexpr int WAVES = KS == 2 ? 4 : 3;
+    static constexpr int SEGS = KS == 2 ? 2 : 1;       // tap rows staged per workgroup
+    static constexpr int BPS = KS / SEGS;              // workgroups per ci slice: one per group of SEGS tap rows
+    static constexpr int ROWS = WG_KQ + KS - 1;        // positions of one tap row: the chunk's and the dx behind them
+    static constexpr int A_FL = SEGS * ROWS * 32;      // floats
+    static constexpr size_t lds_bytes(int nt) { return (A_FL + WG_KQ * nt * 32) * sizeof(float); }
+};
+
+template <int KS, int NT>
+__device__ __forceinline__ void wgrad_f32_taps(const WgradArgs &a)
 {
+    using S = WgradF32Shape<KS>;
+    constexpr int TAPS = KS * KS, THREADS = 64 * S::WAVES, SEGS = S::SEGS, BPS = S::BPS, ROWS = S::ROWS, A_FL = S::A_FL;
     constexpr int NP = NT * 32;
-    constexpr int A_FL = 2 * 33 * 32;      // floats
-    constexpr int NA = 3;                  // 528 float4 / 256 threads
-    constexpr int G_F4 = WG_KQ * NP / 4;   // float4s
-    constexpr int NG = G_F4 / 256;         // == NT
+    constexpr int A_F4 = A_FL / 4;
+    constexpr int NA = (A_F4 + THREADS - 1) / THREADS;
+    constexpr int G_F4 = WG_KQ * NP / 4;
+    constexpr int NG = (G_F4 + THREADS - 1) / THREADS;
+    static_assert(KS == 3 || G_F4 % THREADS == 0, "2x2: the gradient tile is a whole number of staging rounds (no guard)");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *As = reinterpret_cast<float *>(smem);
     float *Gs = As + A_FL;
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63, t = tid >> 6;
+    const int lane = tid & 63, wv = tid >> 6;
     const int i = lane & 31, kh = lane >> 5;
-    int slice, split;
-    if (!wgrad_block_map(a, slice, split)) return;
+    int sd, split;
+    if (!wgrad_block_map(a, sd, split)) return;
+    const int slice = sd / BPS, dy = sd - BPS * slice;
     const int ci0 = slice * 32;
     int c_begin = split * a.chunks_per_split;
     int c_end = c_begin + a.chunks_per_split;
@@ -93,35 +114,37 @@ __global__ __launch_bounds__(256, 2) void wgrad4tap_kernel(WgradArgs a)
 
     float4 ra[NA], rg[NG];
     auto gload = [&](int c) {
-        const long long Qc = (long long)c * WG_KQ;
+        const long long Qc = (long long)c * WG_KQ + (long long)dy * a.P;
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
-            const int idx = tid + 256 * j;
+            const int idx = tid + THREADS * j;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (idx < 528) {
+            if (idx < A_F4) {
                 const int row = idx >> 3, f = idx & 7;
-                const int seg = row >= 33, pix = row - 33 * seg;
+                const int seg = SEGS > 1 && row >= ROWS, pix = row - ROWS * seg;
                 const int ch = ci0 + 4 * f;
                 if (ch < a.cs_in)
                     v = *reinterpret_cast<const float4 *>(a.in + (size_t)(Qc + seg * a.P + pix) * a.cs_in + ch);
             }
             ra[j] = v;
         }
+        const long long Qg = (long long)c * WG_KQ + a.g_shift;
 #pragma unroll
         for (int j = 0; j < NG; ++j) {
-            const int idx = tid + 256 * j;
-            const int row = idx / (NP / 4), f = idx - row * (NP / 4);
+            const int idx = tid + THREADS * j;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (4 * f < a.cs_g)
-                v = *reinterpret_cast<const float4 *>(a.g + (size_t)(Qc + a.g_shift + row) * a.cs_g + 4 * f);
+            if (KS == 2 || idx < G_F4) {
+                const int row = idx / (NP / 4), f = idx - row * (NP / 4);
+                if (4 * f < a.cs_g) v = *reinterpret_cast<const float4 *>(a.g + (size_t)(Qg + row) * a.cs_g + 4 * f);
+            }
             rg[j] = v;
         }
     };
     auto lstore = [&]() {
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
-            const int idx = tid + 256 * j;
-            if (idx < 528) {
+            const int idx = tid + THREADS * j;
+            if (idx < A_F4) {
                 float4 v = ra[j];          // ones row (bias gradient) patched at store time
                 const int ch = ci0 + 4 * (idx & 7);
                 if (ch == a.cin) v.x = 1.f;
@@ -132,16 +155,20 @@ __global__ __launch_bounds__(256, 2) void wgrad4tap_kernel(WgradArgs a)
             }
         }
 #pragma unroll
-        for (int j = 0; j < NG; ++j) reinterpret_cast<float4 *>(Gs)[tid + 256 * j] = rg[j];
+        for (int j = 0; j < NG; ++j) {
+            const int idx = tid + THREADS * j;
+            if (KS == 2 || idx < G_F4) reinterpret_cast<float4 *>(Gs)[idx] = rg[j];
+        }
     };
 
+    const int seg = KS == 2 ? wv >> 1 : 0, dx = KS == 2 ? wv & 1 : wv;   // this wave's tap: row dy + seg, column dx
     if (c_begin < c_end) {
         gload(c_begin);
         for (int c = c_begin; c < c_end; ++c) {
             lstore();
             __syncthreads();
             if (c + 1 < c_end) gload(c + 1);
-            const float *ap = As + ((t >> 1) * 33 + (t & 1) + kh) * 32 + i;
+            const float *ap = As + (seg * ROWS + dx + kh) * 32 + i;
             const float *gp = Gs + kh * NP + i;
 #pragma unroll
             for (int s = 0; s < WG_KQ / 2; ++s) {
@@ -155,8 +182,8 @@ __global__ __launch_bounds__(256, 2) void wgrad4tap_kernel(WgradArgs a)
             __syncthreads();
         }
     }
-    const int CIP = a.nslice * 32;
-    float *pp = a.part + ((size_t)(split * 4 + t) * CIP + ci0) * NP;
+    const int CIP = a.nslice / BPS * 32;
+    float *pp = a.part + ((size_t)(split * TAPS + KS * (dy + seg) + dx) * CIP + ci0) * NP;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -164,6 +191,18 @@ __global__ __launch_bounds__(256, 2) void wgrad4tap_kernel(WgradArgs a)
             const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
             pp[(size_t)row * NP + 32 * nt + i] = acc[nt][r];
         }
+}
+
+template <int NT>
+__global__ __launch_bounds__(256, 2) void wgrad4tap_kernel(WgradArgs a)
+{
+    wgrad_f32_taps<2, NT>(a);
+}
+
+template <int NT>
+__global__ __launch_bounds__(192, 2) void wgrad9tap_kernel(WgradArgs a)
+{
+    wgrad_f32_taps<3, NT>(a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -739,7 +778,7 @@ __global__ void wgrad_reduce_kernel(const float *__restrict__ part, float *__res
     if (ci == Cin) {
         gb[co] = accumulate ? gb[co] + (float)s : (float)s;
     } else {
-        const size_t o = ((size_t)co * Cin + ci) * NTAP + (NTAP == 4 ? master_tap(t, variant) : master_tap9(t, variant));
+        const size_t o = ((size_t)co * Cin + ci) * NTAP + master_tap<(NTAP == 4 ? 2 : 3)>(t, variant);
         gw[o] = accumulate ? gw[o] + (float)s : (float)s;
     }
 }
@@ -769,7 +808,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wave_kernel(const float *__r
     if (ci == Cin) {
         gb[co] = accumulate ? gb[co] + (float)acc : (float)acc;
     } else {
-        const size_t o = ((size_t)co * Cin + ci) * 4 + master_tap(t, variant);
+        const size_t o = ((size_t)co * Cin + ci) * 4 + master_tap<2>(t, variant);
         gw[o] = accumulate ? gw[o] + (float)acc : (float)acc;
     }
 }
@@ -838,12 +877,14 @@ extern "C" int64_t mmlf_wgrad_workspace_floats(int Cin, int Cout, int B, int H, 
     return n + 2 * (make_grid(B, H, W).NQpad / WG_KQ) + 4;  // + the f16 split's per-chunk operand scales and the two tensor scales
 }
 
-template <int NT>
-static int launch_wgrad(const WgradArgs &a, hipStream_t st)
+template <int KS, int NT>
+static int launch_wgrad_f32(const WgradArgs &a, hipStream_t st)
 {
-    constexpr size_t lds = (2 * 33 * 32 + WG_KQ * NT * 32) * sizeof(float);
-    hipLaunchKernelGGL(wgrad4tap_kernel<NT>, dim3(wgrad_grid_blocks(a.nslice, a.nsplit)), dim3(256), lds, st, a);
-    return mmlf_launch_status("mmlf_conv2x2_wgrad");
+    using S = WgradF32Shape<KS>;
+    const dim3 grid(wgrad_grid_blocks(a.nslice, a.nsplit)), block(64 * S::WAVES);
+    if constexpr (KS == 2) hipLaunchKernelGGL(wgrad4tap_kernel<NT>, grid, block, S::lds_bytes(NT), st, a);
+    else hipLaunchKernelGGL(wgrad9tap_kernel<NT>, grid, block, S::lds_bytes(NT), st, a);
+    return mmlf_launch_status(KS == 2 ? "mmlf_conv2x2_wgrad" : "mmlf_conv3x3_wgrad");
 }
 
 template <int MB, int NB, int PL>
@@ -880,6 +921,56 @@ static int launch_wgrad_split(const Wgrad16Cfg &c, const WgradArgs &a, hipStream
     case 38: return launch_wgrad16<3, 8, PL>(a, st);
     default: return launch_wgrad_wide<PL>(a, st);
     }
+}
+
+// the launch arguments every weight-gradient entry point fills the same way; alloc = positions the tensors' allocation
+// rule gives them, part_floats = floats of partial sums the workspace holds
+static WgradArgs wgrad_args(const float *in, int cs_in, int Cin, const float *g, int cs_g, int g_shift, float *workspace,
+                            const Grid &gr, long long alloc, long long part_floats)
+{
+    WgradArgs a = {};
+    a.in = in; a.g = g; a.part = workspace; a.NQpad = gr.NQpad;
+    a.cs_in = cs_in; a.cin = Cin; a.cs_g = cs_g; a.g_shift = g_shift; a.P = gr.P;
+    a.in_bytes = alloc * cs_in * 4; a.g_bytes = alloc * cs_g * 4;
+    a.part_floats = part_floats;
+    a.nchunks = (int)(gr.NQpad / WG_KQ);
+    return a;
+}
+// the launch grid: nslice slice blocks (wgrad_block_map) x nsplit splits of the positions
+static void wgrad_set_grid(WgradArgs &a, int nslice, int nsplit)
+{
+    a.nslice = nslice;
+    a.nsplit = nsplit;
+    a.chunks_per_split = (a.nchunks + nsplit - 1) / nsplit;
+}
+
+// sum the launch's partial sums [a.nsplit][KS*KS][CIP][NP] into the OIHW gradient
+template <int KS>
+static int wgrad_reduce(const WgradArgs &a, float *gw, float *gb, int Cin, int Cout, int CIP, int NP, int variant,
+                        int accumulate, hipStream_t st)
+{
+    const int total = KS * KS * (Cin + 1) * Cout;
+    hipLaunchKernelGGL(wgrad_reduce_kernel<KS * KS>, dim3((total + 255) / 256), dim3(256), 0, st, a.part, gw, gb, Cin, Cout,
+                       CIP, NP, a.nsplit, variant, accumulate);
+    return mmlf_launch_status(KS == 2 ? "mmlf_conv2x2_wgrad(reduce)" : "mmlf_conv3x3_wgrad(reduce)");
+}
+
+// exact-f32 weight gradient of a KS x KS filter: nt = pick_nt(Cout) 32-column tiles, 32-channel ci slices (+1: the ones row
+// that yields the bias gradient), BPS workgroups per slice
+template <int KS>
+static int wgrad_f32(WgradArgs &a, int nt, float *gw, float *gb, int Cin, int Cout, int variant, int accumulate, hipStream_t st)
+{
+    const int ci_slices = (Cin + 1 + 31) / 32, nslice = WgradF32Shape<KS>::BPS * ci_slices;
+    wgrad_set_grid(a, nslice, wgrad_nsplit(nslice));
+    int rc;
+    switch (nt) {
+    case 1: rc = launch_wgrad_f32<KS, 1>(a, st); break;
+    case 3: rc = launch_wgrad_f32<KS, 3>(a, st); break;
+    case 4: rc = launch_wgrad_f32<KS, 4>(a, st); break;
+    default: rc = launch_wgrad_f32<KS, 9>(a, st); break;
+    }
+    if (rc) return rc;
+    return wgrad_reduce<KS>(a, gw, gb, Cin, Cout, ci_slices * 32, nt * 32, variant, accumulate, st);
 }
 
 // planes: 0 = exact-f32 MFMA, 3 = bf16 split, 2 = f16 split (needs in_amax / g_amax)
@@ -925,18 +1016,10 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
     MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_conv2x2_wgrad: bad variant");
     Grid gr = make_grid(B, H, W);
     MMLF_CHECK_ARG(g_shift >= 0 && g_shift <= gr.P + 1, "mmlf_conv2x2_wgrad: g_shift=%d", g_shift);
-    WgradArgs a = {};
-    a.in = in; a.g = g; a.part = workspace; a.NQpad = gr.NQpad;
-    a.cs_in = cs_in; a.cin = Cin; a.cs_g = cs_g; a.g_shift = g_shift; a.P = gr.P;
-    a.in_amax = in_amax; a.g_amax = g_amax; a.chunk_scales = nullptr;
-    a.in_bytes = grid_alloc_positions(gr) * cs_in * 4; a.g_bytes = grid_alloc_positions(gr) * cs_g * 4;
-    a.part_floats = wgrad_partial_floats(Cin, Cout);
-    a.nslice = (Cin + 1 + 31) / 32;   // +1: the ones row that yields the bias gradient
-    a.nsplit = wgrad_nsplit(a.nslice);
-    a.nchunks = (int)(gr.NQpad / WG_KQ);
-    a.chunks_per_split = (a.nchunks + a.nsplit - 1) / a.nsplit;
+    WgradArgs a = wgrad_args(in, cs_in, Cin, g, cs_g, g_shift, workspace, gr, grid_alloc_positions(gr),
+                             wgrad_partial_floats(Cin, Cout));
+    a.in_amax = in_amax; a.g_amax = g_amax;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
     Wgrad16Cfg c;
     if (planes == 2) {          // per-chunk operand scales, behind the partial sums in the workspace
         MMLF_CHECK_ARG(gr.NQpad + 2 * gr.P + 64 < (1ll << 31), "mmlf_conv2x2_wgrad_h2: batch x image too large");
@@ -949,27 +1032,12 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
         a.chunk_scales = ca.out;
     }
     if (planes && wgrad16_cfg(Cin, Cout, a.nchunks, &c)) {
-        a.nslice = c.nslice;
-        a.nsplit = c.nsplit;
-        a.chunks_per_split = (a.nchunks + a.nsplit - 1) / a.nsplit;
-        rc = planes == 3 ? launch_wgrad_split<3>(c, a, st) : launch_wgrad_split<2>(c, a, st);
+        wgrad_set_grid(a, c.nslice, c.nsplit);
+        const int rc = planes == 3 ? launch_wgrad_split<3>(c, a, st) : launch_wgrad_split<2>(c, a, st);
         if (rc) return rc;
-        const int total = 4 * (Cin + 1) * Cout;
-        hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((total + 255) / 256), dim3(256), 0, st, workspace, gw, gb, Cin,
-                           Cout, a.nslice * 16 * c.mb, 16 * c.nb, a.nsplit, variant, accumulate);
-        return mmlf_launch_status("mmlf_conv2x2_wgrad(reduce)");
+        return wgrad_reduce<2>(a, gw, gb, Cin, Cout, a.nslice * 16 * c.mb, 16 * c.nb, variant, accumulate, st);
     }
-    switch (nt) {
-    case 1: rc = launch_wgrad<1>(a, st); break;
-    case 3: rc = launch_wgrad<3>(a, st); break;
-    case 4: rc = launch_wgrad<4>(a, st); break;
-    default: rc = launch_wgrad<9>(a, st); break;
-    }
-    if (rc) return rc;
-    const int total = 4 * (Cin + 1) * Cout;
-    hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((total + 255) / 256), dim3(256), 0, st, workspace, gw, gb, Cin,
-                       Cout, a.nslice * 32, nt * 32, a.nsplit, variant, accumulate);
-    return mmlf_launch_status("mmlf_conv2x2_wgrad(reduce)");
+    return wgrad_f32<2>(a, nt, gw, gb, Cin, Cout, variant, accumulate, st);
 }
 
 // weight + bias gradient of a thin convolution: wave-private sums over its positions, reduced by wgrad_reduce_kernel.
@@ -1102,120 +1170,9 @@ extern "C" int mmlf_audit_wgrad_h2(int cs_in, int Cin, int cs_g, int Cout, int g
 }
 
 // ---------------------------------------------------------------------------------------------
-// weight + bias gradient of the 3x3 ("same", pad 1) convolution, exact-f32 MFMA:
-//   gw[co][ci][tap] (+)= sum_q in[q + dy*P + dx][ci] * g[q + P + 1][co],  gb[co] (+)= sum_q g[q + P + 1][co]
-// The decomposition of wgrad4tap_kernel with one tap ROW per workgroup: 192 threads = 3 waves, wave = dx; block =
-// (32-channel ci slice, dy, position split), so that nine accumulator sets of up to 9 x 16 registers never share a
-// workgroup.  The gradient tile is staged once per (slice, dy) block; the three dy blocks of a slice read it from L2.
+// weight + bias gradient of the 3x3 ("same", pad 1) convolution, exact-f32 MFMA (wgrad9tap_kernel = wgrad_f32_taps<3, NT>
+// above, g_shift = P + 1): entry points
 // ---------------------------------------------------------------------------------------------
-template <int NT>
-__global__ __launch_bounds__(192, 2) void wgrad9tap_kernel(WgradArgs a)
-{
-    constexpr int NP = NT * 32;
-    constexpr int ROWS = WG_KQ + 2;        // positions of one tap row: the chunk's 32 and the two dx behind them
-    constexpr int A_FL = ROWS * 32;        // floats
-    constexpr int A_F4 = A_FL / 4;         // 272
-    constexpr int NA = (A_F4 + 191) / 192;
-    constexpr int G_F4 = WG_KQ * NP / 4;
-    constexpr int NG = (G_F4 + 191) / 192;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *As = reinterpret_cast<float *>(smem);
-    float *Gs = As + A_FL;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, dx = tid >> 6;
-    const int i = lane & 31, kh = lane >> 5;
-    int sd, split;
-    if (!wgrad_block_map(a, sd, split)) return;
-    const int slice = sd / 3, dy = sd - 3 * slice;
-    const int ci0 = slice * 32;
-    int c_begin = split * a.chunks_per_split;
-    int c_end = c_begin + a.chunks_per_split;
-    if (c_end > a.nchunks) c_end = a.nchunks;
-
-    f32x16 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-
-    float4 ra[NA], rg[NG];
-    auto gload = [&](int c) {
-        const long long Qc = (long long)c * WG_KQ + (long long)dy * a.P;
-#pragma unroll
-        for (int j = 0; j < NA; ++j) {
-            const int idx = tid + 192 * j;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (idx < A_F4) {
-                const int row = idx >> 3, ch = ci0 + 4 * (idx & 7);
-                if (ch < a.cs_in) v = *reinterpret_cast<const float4 *>(a.in + (size_t)(Qc + row) * a.cs_in + ch);
-            }
-            ra[j] = v;
-        }
-        const long long Qg = (long long)c * WG_KQ + a.g_shift;
-#pragma unroll
-        for (int j = 0; j < NG; ++j) {
-            const int idx = tid + 192 * j;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (idx < G_F4) {
-                const int row = idx / (NP / 4), f = idx - row * (NP / 4);
-                if (4 * f < a.cs_g) v = *reinterpret_cast<const float4 *>(a.g + (size_t)(Qg + row) * a.cs_g + 4 * f);
-            }
-            rg[j] = v;
-        }
-    };
-    auto lstore = [&]() {
-#pragma unroll
-        for (int j = 0; j < NA; ++j) {
-            const int idx = tid + 192 * j;
-            if (idx < A_F4) {
-                float4 v = ra[j];          // ones row (bias gradient) patched at store time
-                const int ch = ci0 + 4 * (idx & 7);
-                if (ch == a.cin) v.x = 1.f;
-                if (ch + 1 == a.cin) v.y = 1.f;
-                if (ch + 2 == a.cin) v.z = 1.f;
-                if (ch + 3 == a.cin) v.w = 1.f;
-                reinterpret_cast<float4 *>(As)[idx] = v;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NG; ++j) {
-            const int idx = tid + 192 * j;
-            if (idx < G_F4) reinterpret_cast<float4 *>(Gs)[idx] = rg[j];
-        }
-    };
-
-    if (c_begin < c_end) {
-        gload(c_begin);
-        for (int c = c_begin; c < c_end; ++c) {
-            lstore();
-            __syncthreads();
-            if (c + 1 < c_end) gload(c + 1);
-            const float *ap = As + (dx + kh) * 32 + i;
-            const float *gp = Gs + kh * NP + i;
-#pragma unroll
-            for (int s = 0; s < WG_KQ / 2; ++s) {
-                const float av = ap[2 * s * 32];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float bv = gp[2 * s * NP + 32 * nt];
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[nt], 0, 0, 0);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    const int CIP = a.nslice / 3 * 32;
-    float *pp = a.part + ((size_t)(split * 9 + 3 * dy + dx) * CIP + ci0) * NP;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-            pp[(size_t)row * NP + 32 * nt + i] = acc[nt][r];
-        }
-}
-
 // launch layout of the 3x3 weight gradient: 3 * (ci slices) x position splits
 struct Wgrad9Cfg { int nt, nslice, nsplit; };
 static inline bool wgrad9_cfg(int Cin, int Cout, Wgrad9Cfg *c)
@@ -1234,14 +1191,6 @@ extern "C" int64_t mmlf_wgrad3x3_workspace_floats(int Cin, int Cout, int B, int 
     return (int64_t)c.nsplit * 9 * (c.nslice / 3 * 32) * (c.nt * 32);
 }
 
-template <int NT>
-static int launch_wgrad9(const WgradArgs &a, hipStream_t st)
-{
-    constexpr size_t lds = ((WG_KQ + 2) * 32 + WG_KQ * NT * 32) * sizeof(float);
-    hipLaunchKernelGGL(wgrad9tap_kernel<NT>, dim3(wgrad_grid_blocks(a.nslice, a.nsplit)), dim3(192), lds, st, a);
-    return mmlf_launch_status("mmlf_conv3x3_wgrad");
-}
-
 extern "C" int mmlf_conv3x3_wgrad(const float *in, int cs_in, int Cin, const float *g, int cs_g, int Cout, float *gw_oihw,
                                   float *gb, int variant, int accumulate, float *workspace, int B, int H, int W, void *stream)
 {
@@ -1254,28 +1203,9 @@ extern "C" int mmlf_conv3x3_wgrad(const float *in, int cs_in, int Cin, const flo
     MMLF_CHECK_ARG(wgrad9_cfg(Cin, Cout, &c), "mmlf_conv3x3_wgrad: Cout=%d not supported", Cout);
     const Grid gr = make_grid(B, H, W);
     MMLF_CHECK_ARG(gr.NQpad + 2 * gr.P + 64 < (1ll << 31), "mmlf_conv3x3_wgrad: batch x image too large");
-    WgradArgs a = {};
-    a.in = in; a.g = g; a.part = workspace; a.NQpad = gr.NQpad;
-    a.cs_in = cs_in; a.cin = Cin; a.cs_g = cs_g; a.g_shift = gr.P + 1; a.P = gr.P;
-    a.in_bytes = grid_alloc_positions_k3(gr) * cs_in * 4; a.g_bytes = grid_alloc_positions_k3(gr) * cs_g * 4;
-    a.part_floats = mmlf_wgrad3x3_workspace_floats(Cin, Cout, B, H, W);
-    a.nslice = c.nslice;
-    a.nsplit = c.nsplit;
-    a.nchunks = (int)(gr.NQpad / WG_KQ);
-    a.chunks_per_split = (a.nchunks + a.nsplit - 1) / a.nsplit;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    switch (c.nt) {
-    case 1: rc = launch_wgrad9<1>(a, st); break;
-    case 3: rc = launch_wgrad9<3>(a, st); break;
-    case 4: rc = launch_wgrad9<4>(a, st); break;
-    default: rc = launch_wgrad9<9>(a, st); break;
-    }
-    if (rc) return rc;
-    const int total = 9 * (Cin + 1) * Cout;
-    hipLaunchKernelGGL(wgrad_reduce_kernel<9>, dim3((total + 255) / 256), dim3(256), 0, st, workspace, gw_oihw, gb, Cin,
-                       Cout, c.nslice / 3 * 32, c.nt * 32, c.nsplit, variant, accumulate);
-    return mmlf_launch_status("mmlf_conv3x3_wgrad(reduce)");
+    WgradArgs a = wgrad_args(in, cs_in, Cin, g, cs_g, gr.P + 1, workspace, gr, grid_alloc_positions_k3(gr),
+                             mmlf_wgrad3x3_workspace_floats(Cin, Cout, B, H, W));
+    return wgrad_f32<3>(a, c.nt, gw_oihw, gb, Cin, Cout, variant, accumulate, (hipStream_t)stream);
 }
 
 // Bounds audit of one mmlf_conv3x3_wgrad launch (ends[MMLF_AUDIT_WG_IN .. MMLF_AUDIT_WG_WORKSPACE]): chunk c stages

@@ -84,6 +84,26 @@ def test_weight_gradient_kernels_do_not_spill_and_leave_room_for_batchnorm(usage
     assert rows_bwd[0] <= 48 and rows_bwd[2] == 0, rows_bwd
 
 
+# waves per SIMD of the exact-f32 kernels, per NT, as measured before the 2x2 and 3x3 twins were given one shared body each
+F32_OCCUPANCY = {
+    'conv4tap_kernel': {1: 8, 3: 5, 4: 4, 9: 2},
+    'conv9tap_kernel': {1: 8, 3: 4, 4: 3},
+    'wgrad4tap_kernel': {1: 7, 3: 4, 4: 4, 9: 2},
+    'wgrad9tap_kernel': {1: 7, 3: 4, 4: 4, 9: 2},
+}
+
+
+@pytest.mark.parametrize('stem', sorted(F32_OCCUPANCY))
+def test_exact_f32_kernels_keep_their_occupancy_without_scratch(usage, stem):
+    """the 2x2 and 3x3 entry points instantiate one body per family (conv_f32_taps, wgrad_f32_taps): neither filter size may
+    pay for the other's constants with a spill or a lost wave (wgrad9tap_kernel<9> sits a few registers below the 256 that
+    two waves per SIMD allow)"""
+    for nt, waves in F32_OCCUPANCY[stem].items():
+        v = _demangled(usage, stem, (nt,))
+        assert v[2] == 0, (stem, nt, v)
+        assert v[3] >= waves, (stem, nt, v)
+
+
 def test_register_streamed_full_frame_kinds(usage):
     """the evaluation path's narrow launches (ReLU, 27 -> 70 and 70 -> 70) hold their 2 waves per SIMD without scratch"""
     for nch in (4, 9):

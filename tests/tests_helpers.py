@@ -29,7 +29,7 @@ def variant_filter(w, variant, inverse=False):
 # matmuls in whatever dtype / device the operands have (float64 for the tests); no convolution library is involved.
 
 def master9(variant):
-    """packed tap t = dy*3 + dx -> tap of the OIHW master filter (csrc/common.h master_tap9)"""
+    """packed tap t = dy*3 + dx -> tap of the OIHW master filter (csrc/common.h master_tap<3>)"""
     taps = []
     for t in range(9):
         dy, dx = divmod(t, 3)
