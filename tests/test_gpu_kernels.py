@@ -129,7 +129,8 @@ def test_filter_variants_equal_image_transforms(oracle, variant):
     np.testing.assert_allclose(got, ref, rtol=2e-5, atol=2e-5)
 
 
-@pytest.mark.parametrize('cin,cout', [(27, 70), (70, 70), (280, 280), (280, 2), (2, 2), (280, 108), (32, 8), (79, 80), (31, 33)])
+@pytest.mark.parametrize('cin,cout', [(27, 70), (70, 70), (280, 280), (280, 2), (2, 2), (280, 108), (32, 8), (79, 80), (31, 33),
+                                      (108, 108)])
 @pytest.mark.parametrize('pad', [1, 0])
 @pytest.mark.parametrize('variant', [0, 2])
 @pytest.mark.parametrize('mode', ['f32', 'bf16x6', 'f16x3'])
@@ -331,7 +332,7 @@ def test_error_convention():
              None, 0, None)
 
 
-@pytest.mark.parametrize('mode', ['bf16x6', 'f16x3'])
+@pytest.mark.parametrize('mode', ['f32', 'bf16x6', 'f16x3'])
 @pytest.mark.parametrize('cin,cout,pad', [(280, 280, 1), (280, 280, 0), (70, 70, 1), (27, 70, 1)])
 def test_full_size_adjoint_identities(cin, cout, pad, mode, monkeypatch):
     """BASELINE.json's full size (bs=512, ps=96), where the oracle is too slow: the three conv kernels must be

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 
 from conftest import BASE_KW, TINY_KW, VARIANTS, load_golden
 from mmlf_amd import synth
-from tests_helpers import conv9_ref, dgrad9_ref, filter9, unfilter9, wgrad9_ref
+from tests_helpers import check_sum_bar, conv9_ref, dgrad9_ref, filter9, unfilter9, wgrad9_ref
 
 pytestmark = pytest.mark.gpu
 K3_TINY_KW = dict(TINY_KW, model_ksize=3)
@@ -67,10 +67,7 @@ def _grid_view(geo, g, cs):
     return g[:geo.NQ * cs].view(geo.B, geo.R, geo.P, cs)
 
 
-def _check(got, ref, bound, what, tol=2e-5):
-    err = (got - ref).abs()
-    lim = tol * bound + 1e-6 * float(bound.max()) + 1e-30
-    assert bool((err <= lim).all()), (what, float((err / lim).max()))
+_check = check_sum_bar          # 2e-5 * sum|a||b| + 1e-6 * max (tests_helpers.py; shared with tests/test_gpu_backward2x2.py)
 
 
 @pytest.mark.parametrize('variant', [0, 1, 2])

@@ -76,3 +76,74 @@ def wgrad9_ref(xg, gg):
         for dx in range(3):
             gw[:, :, dy, dx] = gv.t() @ xg[:, dy:dy + H, dx:dx + W, :].reshape(-1, K)
     return gw, gv.sum(0)
+
+
+# ------------------------------------------------------------------ 2x2 float64 references on the grid layout
+# The 2x2 kernels read q + dy*P + dx and write q + out_shift (include/mmlf_hip.h).  On the grid view (B, H + 2, W + 2, C):
+#   pad 1: input extent (H, W) at (1, 1)       -> output extent (H + 1, W + 1) at (0, 0), out_shift = 0
+#   pad 0: input extent (H + 1, W + 1) at (0, 0) -> output extent (H, W) at (1, 1),       out_shift = P + 1
+# Either way out[b, r, c] = sum_{dy, dx} xg[b, r + dy, c + dx] @ w_v[:, :, dy, dx].T over the output's extent (h, w); the
+# references return that extent alone, the caller places it.  Plain per-tap matmuls, as conv9_ref.
+
+def filter4(w, variant):
+    """the filter the kernels apply on the grid for a stream variant: w_v[..., dy, dx] = w[..., master(dy, dx)]"""
+    out = w.new_zeros(w.shape)
+    for dy in range(2):
+        for dx in range(2):
+            sy, sx = _master(dy, dx, variant)
+            out[..., dy, dx] = w[..., sy, sx]
+    return out
+
+
+def unfilter4(gv, variant):
+    """a gradient with respect to filter4(w, variant), scattered back to the master filter's taps"""
+    out = gv.new_zeros(gv.shape)
+    for dy in range(2):
+        for dx in range(2):
+            sy, sx = _master(dy, dx, variant)
+            out[..., sy, sx] = gv[..., dy, dx]
+    return out
+
+
+def extent4(xg, pad):
+    """(h, w) of the OUTPUT of a pad-`pad` 2x2 convolution whose input lives on the grid view xg (B, H + 2, W + 2, C)"""
+    H, W = xg.shape[1] - 2, xg.shape[2] - 2
+    return (H + 1, W + 1) if pad else (H, W)
+
+
+def conv4_ref(xg, wv, bias=None, pad=1):
+    """xg (B, H+2, W+2, K) zero outside the input's extent, wv (N, K, 2, 2) -> (B, h, w, N), (h, w) = extent4(xg, pad)"""
+    h, w = extent4(xg, pad)
+    out = xg.new_zeros((xg.shape[0], h, w, wv.shape[0]))
+    for dy in range(2):
+        for dx in range(2):
+            out += xg[:, dy:dy + h, dx:dx + w, :] @ wv[:, :, dy, dx].t()
+    return out if bias is None else out + bias
+
+
+def dgrad4_ref(gg, wv, pad=1):
+    """data gradient of conv4_ref(., wv, pad): gg (B, H+2, W+2, N) holds the output gradient where the forward stored its
+    output ((0, 0) for pad 1, (1, 1) for pad 0) -> (B, h, w, K) on the forward INPUT's extent.  The same correlation in the
+    other placement, taps rotated by 180 degrees, channel roles swapped."""
+    return conv4_ref(gg, wv.flip(-1, -2).transpose(0, 1), None, 1 - pad)
+
+
+def wgrad4_ref(xg, gg, pad=1):
+    """weight gradient (N, K, 2, 2) of conv4_ref(xg, ., pad) and bias gradient (N,); gg as in dgrad4_ref"""
+    h, w = extent4(xg, pad)
+    o = 0 if pad else 1
+    gv = gg[:, o:o + h, o:o + w, :].reshape(-1, gg.shape[-1])
+    K = xg.shape[-1]
+    gw = xg.new_zeros((gg.shape[-1], K, 2, 2))
+    for dy in range(2):
+        for dx in range(2):
+            gw[:, :, dy, dx] = gv.t() @ xg[:, dy:dy + h, dx:dx + w, :].reshape(-1, K)
+    return gw, gv.sum(0)
+
+
+def check_sum_bar(got, ref, bound, what, tol=2e-5):
+    """|got - ref| <= tol * sum|a||b| + 1e-6 * max: the bar every float64 comparison of a convolution kernel here uses
+    (`bound` = the same sum over absolute values)"""
+    err = (got - ref).abs()
+    lim = tol * bound + 1e-6 * float(bound.max()) + 1e-30
+    assert bool((err <= lim).all()), (what, float((err / lim).max()))
