@@ -196,7 +196,8 @@ int mmlf_conv2x2_wgrad_h2(const float *in, int cs_in, int Cin, const float *g, i
 
 /* nn.BatchNorm2d training statistics (feed_forward.py:134): per-channel mean / biased variance of
  * the extent-(H,W) tensor z (zero border), running-stat update (unbiased var), and the affine
- * coefficients scale = gamma*invstd, shift = beta - mean*scale.  partial: 2*C*nblocks doubles. */
+ * coefficients scale = gamma*invstd, shift = beta - mean*scale.  partial: 2*C*nblocks doubles.
+ * refuses: cs % 4, C outside [1, min(cs, 1024)], nblocks outside [1, 4096], B, H or W < 1. */
 int mmlf_bn_stats_train(const float *z, int cs, int C, const float *gamma, const float *beta,
                         float *running_mean, float *running_var, double momentum, double eps,
                         float *save_mean, float *save_invstd, float *scale, float *shift,
@@ -213,13 +214,15 @@ int mmlf_fold_bn_eval(const float *w_oihw, const float *bias, const float *scale
 /* The second half of mmlf_bn_stats_train for statistics that the convolution already accumulated:
  * mmlf_conv2x2_h2(bn_partial = partial) writes per-workgroup sums of z and z^2 per channel
  * ([mmlf_conv2x2_blocks()][2][C] doubles) from its epilogue, so the pad-0 convolution's output is not
- * read again for nn.BatchNorm2d's training statistics (feed_forward.py:134). */
+ * read again for nn.BatchNorm2d's training statistics (feed_forward.py:134).
+ * refuses: C < 1, nblocks < 1, B, H or W < 1. */
 int mmlf_bn_stats_finalize(const double *partial, int nblocks, int C, const float *gamma, const float *beta,
                            float *running_mean, float *running_var, double momentum, double eps,
                            float *save_mean, float *save_invstd, float *scale, float *shift,
                            int B, int H, int W, void *stream);
 /* y[q][c_off + c] = interior(q) ? relu(z[q][c]*scale[c] + shift[c]) : 0   (BN apply + nn.ReLU,
- * feed_forward.py:134-135; writing a channel slice implements torch.cat, feed_forward.py:266-267) */
+ * feed_forward.py:134-135; writing a channel slice implements torch.cat, feed_forward.py:266-267)
+ * refuses: cs_z % 4, odd cs_y or c_off, C outside [1, cs_z], C_store < C, a slice past cs_y, B, H or W < 1. */
 int mmlf_bn_apply_relu(const float *z, int cs_z, int C, const float *scale, const float *shift,
                        float *y, int cs_y, int c_off, int C_store, int B, int H, int W,
                        float *amax_out /* nullable: amax array of y */, void *stream);
@@ -230,20 +233,24 @@ int mmlf_bn_apply_relu4(const float *const z[4], int cs_z, int C, const float *c
                         const float *const shift[4], float *y, int cs_y, int B, int H, int W,
                         float *amax_out /* nullable: amax array of y */, void *stream);
 /* BatchNorm2d + ReLU backward, pass 1: per-channel sums of g and g*zhat with
- * g = gy * (z*scale+shift > 0); emits dgamma, dbeta (accumulating) and coefficients k[3*C]. */
+ * g = gy * (z*scale+shift > 0); emits dgamma, dbeta (accumulating) and coefficients k[3*C].
+ * refuses: cs_z % 4, odd cs_gy or c_off, C outside [1, min(cs_z, 512)] (128 groups of four channels), a slice past cs_gy,
+ * nblocks outside [1, 4096], B, H or W < 1. */
 int mmlf_bn_bwd_reduce(const float *gy, int cs_gy, int c_off, const float *z, int cs_z, int C,
                        const float *scale, const float *shift, const float *gamma,
                        const float *save_mean, const float *save_invstd,
                        float *dgamma, float *dbeta, int accumulate, float *coef,
                        double *partial, int nblocks, int B, int H, int W, void *stream);
-/* pass 2: dz[q][c] = interior(q) ? k1*g - k2 - k3*(z - mean) : 0 */
+/* pass 2: dz[q][c] = interior(q) ? k1*g - k2 - k3*(z - mean) : 0
+ * refuses: cs_z % 4, cs_dz % 4, odd cs_gy or c_off, C outside [1, min(cs_z, cs_dz)], a slice past cs_gy, B, H or W < 1. */
 int mmlf_bn_bwd_apply(const float *gy, int cs_gy, int c_off, const float *z, int cs_z, int C,
                       const float *scale, const float *shift, const float *save_mean,
                       const float *coef, float *dz, int cs_dz, int B, int H, int W,
                       float *amax_out /* nullable: amax array of dz */, void *stream);
 
 /* (B, C, H, W) NCHW  <->  padded-grid NHWC (extent (H,W), grid offset (1,1), zero border, zero pad
- * channels).  replaces the .view / layout handling of feed_forward.py:226-232 and output[:, 0]. */
+ * channels).  replaces the .view / layout handling of feed_forward.py:226-232 and output[:, 0].
+ * both refuse: cs % 4, C outside [1, cs], B, H or W < 1. */
 int mmlf_pack_nchw(const float *nchw, int C, float *grid, int cs, int B, int H, int W,
                    float *amax_out /* nullable: amax array of grid */, void *stream);
 int mmlf_unpack_nchw(const float *grid, int cs, float *nchw, int C, int B, int H, int W, void *stream);

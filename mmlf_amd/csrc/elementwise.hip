@@ -254,10 +254,11 @@ __global__ void bn_coeffs_eval_kernel(const float *gamma, const float *beta, con
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float invf = (float)(1.0 / sqrt((double)rv[c] + eps));
-    const float sc = (gamma ? gamma[c] : 1.f) * invf;
+    // one rounding for the scale (the product is taken in double) and one more for the shift (fused): the shift stays within
+    // 2^-23 (|beta| + |rm scale|) of the exact value, which three float32 operations on a rounded invstd do not promise
+    const float sc = (float)((double)(gamma ? gamma[c] : 1.f) * (1.0 / sqrt((double)rv[c] + eps)));
     scale[c] = sc;
-    shift[c] = (beta ? beta[c] : 0.f) - rm[c] * sc;
+    shift[c] = fmaf(-rm[c], sc, beta ? beta[c] : 0.f);
 }
 
 __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const double *__restrict__ partial, int nblocks, int C,
@@ -1327,6 +1328,7 @@ extern "C" int mmlf_bn_stats_train(const float *z, int cs, int C, const float *g
     MMLF_CHECK_ARG(z && save_mean && save_invstd && scale && shift && partial, "mmlf_bn_stats_train: null pointer");
     MMLF_CHECK_ARG(cs % 4 == 0 && C > 0 && C <= cs && (C + 3) / 4 <= 256, "mmlf_bn_stats_train: C=%d cs=%d", C, cs);
     MMLF_CHECK_ARG(nblocks > 0 && nblocks <= 4096, "mmlf_bn_stats_train: nblocks=%d", nblocks);
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_bn_stats_train: bad shape B=%d H=%d W=%d", B, H, W);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL((bn_reduce_kernel<4>), dim3(nblocks), dim3(256), 0, st, z, cs, nullptr, 0, 0, nullptr,
                        nullptr, nullptr, nullptr, C, partial, B, H, W);
@@ -1343,6 +1345,7 @@ extern "C" int mmlf_bn_stats_finalize(const double *partial, int nblocks, int C,
 {
     MMLF_CHECK_ARG(partial && save_mean && save_invstd && scale && shift && C > 0 && nblocks > 0,
                    "mmlf_bn_stats_finalize: bad argument");
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_bn_stats_finalize: bad shape B=%d H=%d W=%d", B, H, W);
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, partial, nblocks, C,
                        (double)B * H * W, gamma, beta, running_mean, running_var, momentum, eps, save_mean,
                        save_invstd, scale, shift);
@@ -1386,9 +1389,10 @@ extern "C" int mmlf_bn_apply_relu(const float *z, int cs_z, int C, const float *
                                   void *stream)
 {
     MMLF_CHECK_ARG(z && scale && shift && y, "mmlf_bn_apply_relu: null pointer");
-    MMLF_CHECK_ARG(cs_z % 4 == 0 && cs_y % 2 == 0 && c_off % 2 == 0 && C <= cs_z && C_store >= C &&
+    MMLF_CHECK_ARG(cs_z % 4 == 0 && cs_y % 2 == 0 && c_off % 2 == 0 && c_off >= 0 && C > 0 && C <= cs_z && C_store >= C &&
                        c_off + C_store <= cs_y,
                    "mmlf_bn_apply_relu: C=%d cs_z=%d cs_y=%d c_off=%d C_store=%d", C, cs_z, cs_y, c_off, C_store);
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_bn_apply_relu: bad shape B=%d H=%d W=%d", B, H, W);
     const int nrows = B * (H + GRID_PAD);
     hipLaunchKernelGGL((bn_rows_kernel<0, 4>), dim3(nrows), dim3(256), 6 * (C_store + 4) * sizeof(float), (hipStream_t)stream, z, cs_z,
                        nullptr, 0, 0, scale, shift, nullptr, nullptr, C, y, cs_y, c_off, C_store, H, W, amax_out, nrows);
@@ -1421,9 +1425,12 @@ extern "C" int mmlf_bn_bwd_reduce(const float *gy, int cs_gy, int c_off, const f
 {
     MMLF_CHECK_ARG(gy && z && scale && shift && save_mean && save_invstd && coef && partial,
                    "mmlf_bn_bwd_reduce: null pointer");
-    MMLF_CHECK_ARG(cs_gy % 2 == 0 && c_off % 2 == 0 && cs_z % 4 == 0 && C <= cs_z && (C + 1) / 2 <= 256,
-                   "mmlf_bn_bwd_reduce: layout");
+    // at most 128 channel groups of four (512 channels, as before in pairs: the callers' partial buffers are sized by it)
+    MMLF_CHECK_ARG(cs_gy % 2 == 0 && c_off % 2 == 0 && c_off >= 0 && cs_z % 4 == 0 && C > 0 && C <= cs_z &&
+                       c_off + C <= cs_gy && (C + 3) / 4 <= 128,
+                   "mmlf_bn_bwd_reduce: layout C=%d cs_z=%d cs_gy=%d c_off=%d", C, cs_z, cs_gy, c_off);
     MMLF_CHECK_ARG(nblocks > 0 && nblocks <= 4096, "mmlf_bn_bwd_reduce: nblocks=%d", nblocks);
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_bn_bwd_reduce: bad shape B=%d H=%d W=%d", B, H, W);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_reduce_bwd_kernel, dim3(nblocks), dim3(256), 0, st, z, cs_z, gy, cs_gy, c_off,
                        scale, shift, save_mean, save_invstd, C, partial, B, H, W);
@@ -1437,8 +1444,10 @@ extern "C" int mmlf_bn_bwd_apply(const float *gy, int cs_gy, int c_off, const fl
                                  float *dz, int cs_dz, int B, int H, int W, float *amax_out, void *stream)
 {
     MMLF_CHECK_ARG(gy && z && scale && shift && save_mean && coef && dz, "mmlf_bn_bwd_apply: null pointer");
-    MMLF_CHECK_ARG(cs_gy % 2 == 0 && c_off % 2 == 0 && cs_z % 4 == 0 && cs_dz % 4 == 0 && C <= cs_dz,
-                   "mmlf_bn_bwd_apply: layout");
+    MMLF_CHECK_ARG(cs_gy % 2 == 0 && c_off % 2 == 0 && c_off >= 0 && cs_z % 4 == 0 && cs_dz % 4 == 0 && C > 0 && C <= cs_z &&
+                       C <= cs_dz && c_off + C <= cs_gy,
+                   "mmlf_bn_bwd_apply: layout C=%d cs_z=%d cs_dz=%d cs_gy=%d c_off=%d", C, cs_z, cs_dz, cs_gy, c_off);
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_bn_bwd_apply: bad shape B=%d H=%d W=%d", B, H, W);
     const int nrows = B * (H + GRID_PAD);
     hipLaunchKernelGGL((bn_rows_kernel<1, 4>), dim3(nrows), dim3(256), 6 * (cs_dz + 4) * sizeof(float), (hipStream_t)stream, z, cs_z, gy,
                        cs_gy, c_off, scale, shift, save_mean, coef, C, dz, cs_dz, 0, cs_dz, H, W, amax_out, nrows);
@@ -1449,6 +1458,7 @@ extern "C" int mmlf_pack_nchw(const float *nchw, int C, float *grid, int cs, int
                               void *stream)
 {
     MMLF_CHECK_ARG(nchw && grid && C > 0 && cs % 4 == 0 && C <= cs, "mmlf_pack_nchw: C=%d cs=%d", C, cs);
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_pack_nchw: bad shape B=%d H=%d W=%d", B, H, W);
     int xt = PACK_XT;            // DPP with many views packs a gradient of 4*views*3 channels (132 at 11 views)
     constexpr size_t tile_limit = 32 * 1024;
     while (xt > 4 && (size_t)cs * (xt | 1) * sizeof(float) > tile_limit) xt >>= 1;
@@ -1542,7 +1552,8 @@ extern "C" int mmlf_zero_slack4_k3(float *const grid[4], const int cs[4], float 
 
 extern "C" int mmlf_unpack_nchw(const float *grid, int cs, float *nchw, int C, int B, int H, int W, void *stream)
 {
-    MMLF_CHECK_ARG(nchw && grid && C > 0 && C <= cs, "mmlf_unpack_nchw: C=%d cs=%d", C, cs);
+    MMLF_CHECK_ARG(nchw && grid && C > 0 && C <= cs && cs % 4 == 0, "mmlf_unpack_nchw: C=%d cs=%d", C, cs);
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_unpack_nchw: bad shape B=%d H=%d W=%d", B, H, W);
     int xt = 32;
     while (xt > 1 && (size_t)xt * (C | 1) * sizeof(float) > 32 * 1024) xt >>= 1;
     hipLaunchKernelGGL(unpack_nchw_kernel, dim3(B * H), dim3(256), (size_t)xt * (C | 1) * sizeof(float), (hipStream_t)stream,

@@ -147,3 +147,64 @@ def check_sum_bar(got, ref, bound, what, tol=2e-5):
     err = (got - ref).abs()
     lim = tol * bound + 1e-6 * float(bound.max()) + 1e-30
     assert bool((err <= lim).all()), (what, float((err / lim).max()))
+
+
+# ------------------------------------------------------------------ BatchNorm2d + ReLU float64 references on the grid layout
+# nn.BatchNorm2d (training statistics, running update, affine) and nn.ReLU with their gradients, over the interior
+# [1, H] x [1, W] of the grid view (B, H + 2, W + 2, C), as plain tensor expressions in whatever dtype / device the operands
+# have (float64 for the tests); no batch_norm call is involved.  Border positions of the operands are never used (they may hold
+# anything); the element-wise results are returned for the whole view, the caller takes the positions it wants.
+
+def _interior(g):
+    return g[:, 1:g.shape[1] - 1, 1:g.shape[2] - 1, :]
+
+
+def bn_stats_ref(zg, gamma, beta, rm, rv, momentum, eps):
+    """zg (B, H+2, W+2, C) -> (mean, invstd, scale, shift, new running mean, new running variance), each (C,).  Biased
+    variance as E[z^2] - E[z]^2 (the order bn_stats_finalize_kernel takes: the inputs keep mean^2 small against it), exactly
+    0 for one element; the running variance takes the unbiased form (the biased one for one element, as the kernel does).
+    gamma / beta / rm / rv may be None (1 / 0 / no running update)."""
+    zi = _interior(zg)
+    n = zi.shape[0] * zi.shape[1] * zi.shape[2]
+    mean = zi.sum((0, 1, 2)) / n
+    var = ((zi * zi).sum((0, 1, 2)) / n - mean * mean).clamp_min(0) if n > 1 else mean * 0
+    invstd = 1 / (var + eps).sqrt()
+    scale = invstd if gamma is None else gamma * invstd
+    shift = -mean * scale if beta is None else beta - mean * scale
+    unb = var * n / (n - 1) if n > 1 else var
+    new_rm = None if rm is None else (1 - momentum) * rm + momentum * mean
+    new_rv = None if rv is None else (1 - momentum) * rv + momentum * unb
+    return mean, invstd, scale, shift, new_rm, new_rv
+
+
+def bn_apply_ref(zg, scale, shift):
+    """u = z * scale + shift (ReLU is the caller's clamp) and the absolute terms |z * scale| + |shift| a rounding bar scales by"""
+    t = zg * scale
+    return t + shift, t.abs() + shift.abs()
+
+
+class BnBwd:
+    """what bn_bwd_ref returns: mask, dgamma, dbeta, k1, k2, k3, dz, and the sums of absolute terms sum_abs_g = sum |g|,
+    sum_abs_gz = sum |g| |zhat|, dz_abs = |k1 g| + |k2| + |k3| |z - mean|"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def bn_bwd_ref(zg, gyg, scale, shift, gamma, mean, invstd):
+    """gradient of relu(batch_norm(z)) in training mode, from the forward's coefficients: g = gy * (u > 0) with
+    u = z * scale + shift; dbeta = sum g, dgamma = sum g * zhat, zhat = (z - mean) * invstd; k1 = gamma * invstd,
+    k2 = k1 * dbeta / n, k3 = k1 * invstd * dgamma / n; dz = k1 * g - k2 - k3 * (z - mean).  mask, dz and dz_abs cover the
+    interior (B, H, W, C); gamma may be None (1)."""
+    z, gy = _interior(zg), _interior(gyg)
+    n = z.shape[0] * z.shape[1] * z.shape[2]
+    mask = z * scale + shift > 0
+    g = gy * mask
+    zc = z - mean
+    zhat = zc * invstd
+    dbeta, dgamma = g.sum((0, 1, 2)), (g * zhat).sum((0, 1, 2))
+    k1 = invstd if gamma is None else gamma * invstd
+    k2, k3 = k1 * dbeta / n, k1 * invstd * dgamma / n
+    return BnBwd(mask=mask, dgamma=dgamma, dbeta=dbeta, k1=k1, k2=k2, k3=k3, dz=k1 * g - k2 - k3 * zc,
+                 sum_abs_g=g.abs().sum((0, 1, 2)), sum_abs_gz=(g.abs() * zhat.abs()).sum((0, 1, 2)),
+                 dz_abs=(k1 * g).abs() + k2.abs() + k3.abs() * zc.abs())
