@@ -41,11 +41,11 @@ const char *mmlf_last_error(void);
 /* Bumped whenever an entry point's arguments or a layout they share changes.  mmlf_abi_version() returns the value the
  * library was BUILT with: a binding compares it with the header it was written against (mmlf_amd/_lib.py does, and reads
  * the number from this line) before making any other call. */
-#define MMLF_ABI_VERSION 9
+#define MMLF_ABI_VERSION 10
 int mmlf_abi_version(void);
 
 /* What the binary is: one line with the ABI version, the source revision it was built from and the bounds-debug switch
- * ("abi=9 git=... src=... MMLF_BOUNDS_DEBUG=0 ablation=0").  mmlf_build_is_ablation() is nonzero for a build that computes
+ * ("abi=10 git=... src=... MMLF_BOUNDS_DEBUG=0 ablation=0").  mmlf_build_is_ablation() is nonzero for a build that computes
  * WRONG results by construction (the timing ablations of older trees; the current sources have none and return 0): a
  * binding must refuse such a library unless its user asked for it (mmlf_amd/_lib.py: MMLF_ALLOW_ABLATION=1). */
 const char *mmlf_build_info(void);
@@ -247,6 +247,21 @@ int mmlf_bn_bwd_apply(const float *gy, int cs_gy, int c_off, const float *z, int
                       const float *scale, const float *shift, const float *save_mean,
                       const float *coef, float *dz, int cs_dz, int B, int H, int W,
                       float *amax_out /* nullable: amax array of dz */, void *stream);
+/* nn.ReLU backward of a channel slice, for blocks without BatchNorm (model_no_batchnorm, feed_forward.py:122-137, where the
+ * stream nets' last ReLU outputs are channel slices of the concat buffer, :266-267):
+ *   dst[q][c] = interior(q) && c < C ? (ref[q][ref_off + c] > 0 ? src[q][c_off + c] : 0) : 0     for c in [0, cs_dst)
+ * -- a select, exact in float32.  dst is a compact grid tensor (zero border, zero pad channels) whose amax array the launch
+ * raises (amax_out nullable).
+ * refuses: odd cs_src, c_off, cs_ref or ref_off, cs_dst % 4, C outside [1, min(cs_dst, 512)], cs_dst > 1024, a slice past cs_src
+ * (or past cs_ref), B, H or W < 1.
+ * mmlf_audit_relu_bwd_slice: END of what one such launch may touch behind src, ref, dst and amax_out. */
+int mmlf_relu_bwd_slice(const float *src, int cs_src, int c_off, const float *ref, int cs_ref, int ref_off, int C,
+                        float *dst, int cs_dst, int B, int H, int W,
+                        float *amax_out /* nullable: amax array of dst */, void *stream);
+enum { MMLF_AUDIT_SLICE_SRC = 0, MMLF_AUDIT_SLICE_REF = 1, MMLF_AUDIT_SLICE_DST = 2, MMLF_AUDIT_SLICE_AMAX = 3,
+       MMLF_AUDIT_SLICE_N = 4 };
+int mmlf_audit_relu_bwd_slice(int cs_src, int c_off, int cs_ref, int ref_off, int C, int cs_dst, int B, int H, int W,
+                              int64_t *ends);
 
 /* (B, C, H, W) NCHW  <->  padded-grid NHWC (extent (H,W), grid offset (1,1), zero border, zero pad
  * channels).  replaces the .view / layout handling of feed_forward.py:226-232 and output[:, 0].

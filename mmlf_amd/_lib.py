@@ -59,6 +59,8 @@ SIGNATURES = {
     'mmlf_bn_apply_relu4': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'mmlf_bn_bwd_reduce': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     'mmlf_bn_bwd_apply': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'mmlf_relu_bwd_slice': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'mmlf_audit_relu_bwd_slice': (_i, [_i] * 9 + [_vp]),
     'mmlf_pack_nchw': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     'mmlf_zero_slack': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'mmlf_zero_slack4': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -370,6 +370,59 @@ __global__ __launch_bounds__(256) void bn_rows_kernel(const float *__restrict__ 
     }
 }
 
+// ReLU backward of a channel slice (model_no_batchnorm: the stream nets' last blocks write ReLU outputs straight into the
+// concat buffer, and the gradient behind that ReLU is a select): dst[q][c] = ref[q][ref_off + c] > 0 ? src[q][c_off + c] : 0 on
+// the interior, zero on the border and in the pad channels -- the compact grid tensor the convolution and weight-gradient DMA
+// can read (a slice at channel offset 70 s is only 8-byte aligned).  Same row walk, VecIO
+// handling and non-temporal streaming as bn_rows_kernel; no coefficients, so no LDS.  The last channel group of a slice whose
+// width is no multiple of four is read element by element: a float4 there would reach into the neighbouring slice (or, in the
+// last slice, past the position).
+template <int V>
+__global__ __launch_bounds__(256) void relu_slice_rows_kernel(const float *__restrict__ src, int cs_src, int c_off,
+                                                              const float *__restrict__ ref, int cs_ref, int ref_off, int C,
+                                                              float *__restrict__ dst, int cs_dst, int H, int W,
+                                                              float *__restrict__ amax, int nrows)
+{
+    const int P = W + GRID_PAD, R = H + GRID_PAD;
+    const int cvn = cs_dst / V;
+    const int dx = 256 / cvn, dc = 256 - dx * cvn;
+    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
+        const int y = row % R;
+        const size_t base = (size_t)row * P;
+        const bool row_in = (y >= 1 && y <= H);
+        int x = threadIdx.x / cvn, cg = threadIdx.x - x * cvn;
+        float mx = 0.f;
+        for (; x < P; x += dx, cg += dc) {
+            if (cg >= cvn) { cg -= cvn; ++x; if (x >= P) break; }
+            float o[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) o[k] = 0.f;
+            if (row_in && x >= 1 && x <= W && V * cg < C) {
+                const float *sp = src + (base + x) * cs_src + c_off + V * cg;
+                const float *rp = ref + (base + x) * cs_ref + ref_off + V * cg;
+                float rr[V];
+                if (V * cg + V - 1 < C) {
+                    VecIO<V>::load_nt(sp, o);
+                    VecIO<V>::load_nt(rp, rr);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < V; ++k) {
+                        const bool in = V * cg + k < C;
+                        o[k] = in ? sp[k] : 0.f;
+                        rr[k] = in ? rp[k] : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < V; ++k) o[k] = rr[k] > 0.f ? o[k] : 0.f;
+            }
+#pragma unroll
+            for (int k = 0; k < V; ++k) mx = fmaxf(mx, fabsf(o[k]));
+            VecIO<V>::store_nt(dst + (base + x) * cs_dst + V * cg, o);
+        }
+        if (amax) mmlf_amax_update_row(mx, amax, row);      // this workgroup wrote grid row `row`
+    }
+}
+
 // BatchNorm apply + ReLU of the four stream nets' last blocks in ONE pass over the concat buffer (torch.cat,
 // reference feed_forward.py:266-267): four launches that each write a 280-byte slice of every 1120-byte position row
 // run at half the rate of a dense pass (partial lines: 2.5 TB/s against 5.1); this one writes whole rows.
@@ -1452,6 +1505,46 @@ extern "C" int mmlf_bn_bwd_apply(const float *gy, int cs_gy, int c_off, const fl
     hipLaunchKernelGGL((bn_rows_kernel<1, 4>), dim3(nrows), dim3(256), 6 * (cs_dz + 4) * sizeof(float), (hipStream_t)stream, z, cs_z, gy,
                        cs_gy, c_off, scale, shift, save_mean, coef, C, dz, cs_dz, 0, cs_dz, H, W, amax_out, nrows);
     return mmlf_launch_status("mmlf_bn_bwd_apply");
+}
+
+static int relu_bwd_slice_args(const char *who, int cs_src, int c_off, int cs_ref, int ref_off, int C, int cs_dst, int B, int H,
+                               int W)
+{
+    // at most 128 channel groups of four, as the BatchNorm passes this one stands in for
+    MMLF_CHECK_ARG(cs_src > 0 && cs_src % 2 == 0 && c_off % 2 == 0 && c_off >= 0 && cs_dst > 0 && cs_dst % 4 == 0 && C > 0 &&
+                       C <= cs_dst && c_off + C <= cs_src && (C + 3) / 4 <= 128 && cs_dst / 4 <= 256,
+                   "%s: layout C=%d cs_src=%d c_off=%d cs_dst=%d", who, C, cs_src, c_off, cs_dst);
+    MMLF_CHECK_ARG(cs_ref > 0 && cs_ref % 2 == 0 && ref_off % 2 == 0 && ref_off >= 0 && ref_off + C <= cs_ref,
+                   "%s: layout C=%d cs_ref=%d ref_off=%d", who, C, cs_ref, ref_off);
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+    return 0;
+}
+
+extern "C" int mmlf_relu_bwd_slice(const float *src, int cs_src, int c_off, const float *ref, int cs_ref, int ref_off, int C,
+                                   float *dst, int cs_dst, int B, int H, int W, float *amax_out, void *stream)
+{
+    MMLF_CHECK_ARG(src && ref && dst, "mmlf_relu_bwd_slice: null pointer");
+    if (relu_bwd_slice_args("mmlf_relu_bwd_slice", cs_src, c_off, cs_ref, ref_off, C, cs_dst, B, H, W)) return 1;
+    const int nrows = B * (H + GRID_PAD);
+    hipLaunchKernelGGL((relu_slice_rows_kernel<4>), dim3(nrows), dim3(256), 0, (hipStream_t)stream, src, cs_src, c_off, ref,
+                       cs_ref, ref_off, C, dst, cs_dst, H, W, amax_out, nrows);
+    return mmlf_launch_status("mmlf_relu_bwd_slice");
+}
+
+// the launch reads the slices of interior positions only (the last one: row H, column W of patch B - 1), writes every
+// position of the B * R grid rows and raises one amax entry per grid row
+extern "C" int mmlf_audit_relu_bwd_slice(int cs_src, int c_off, int cs_ref, int ref_off, int C, int cs_dst, int B, int H, int W,
+                                         int64_t *ends /* [4] */)
+{
+    MMLF_CHECK_ARG(ends, "mmlf_audit_relu_bwd_slice: null pointer");
+    if (relu_bwd_slice_args("mmlf_audit_relu_bwd_slice", cs_src, c_off, cs_ref, ref_off, C, cs_dst, B, H, W)) return 1;
+    const Grid g = make_grid(B, H, W);
+    const long long q_last = ((long long)(B - 1) * g.R + H) * g.P + W;
+    ends[MMLF_AUDIT_SLICE_SRC] = (q_last * cs_src + c_off + C) * 4;
+    ends[MMLF_AUDIT_SLICE_REF] = (q_last * cs_ref + ref_off + C) * 4;
+    ends[MMLF_AUDIT_SLICE_DST] = g.NQ * cs_dst * 4;
+    ends[MMLF_AUDIT_SLICE_AMAX] = (MMLF_AMAX_HEAD + (long long)B * g.R) * 4;
+    return 0;
 }
 
 extern "C" int mmlf_pack_nchw(const float *nchw, int C, float *grid, int cs, int B, int H, int W, float *amax_out,

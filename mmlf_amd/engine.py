@@ -312,6 +312,19 @@ def _check_wgrad_extents(geo, x, cs_in, cin, g, cs_g, cout, g_shift, gw, gb, wor
                     'workspace': (e[4], workspace, 0), 'in_amax': (e[5], ax, 0), 'g_amax': (e[6], ag, 0)})
 
 
+def relu_bwd_slice(geo, src, cs_src, c_off, ref, cs_ref, ref_off, C, dst, cs_dst):
+    """dst = src[..., c_off:c_off + C] where ref[..., ref_off:ref_off + C] > 0, zero elsewhere, as a compact grid tensor"""
+    if CHECK_EXTENTS:
+        import ctypes
+        e = (ctypes.c_int64 * 4)()
+        call('mmlf_audit_relu_bwd_slice', cs_src, c_off, cs_ref, ref_off, C, cs_dst, geo.B, geo.H, geo.W, e)
+        _check_extents(f'relu_bwd_slice C={C} {cs_src}+{c_off} B={geo.B} {geo.H}x{geo.W}', e,
+                       {'src': (e[0], src, 0), 'ref': (e[1], ref, 0), 'dst': (e[2], dst, 0),
+                        'amax': (e[3], getattr(dst, 'absmax', None), 0)})
+    call('mmlf_relu_bwd_slice', ptr(src), cs_src, c_off, ptr(ref), cs_ref, ref_off, C, ptr(dst), cs_dst, geo.B, geo.H, geo.W,
+         ptr(getattr(dst, 'absmax', None)), _lib.stream_ptr())
+
+
 THIN_MAX_N, THIN_MIN_K = 2, 64     # mmlf_conv2x2_thin: at most 2 output channels over at least 64 input channels
 
 
@@ -435,19 +448,28 @@ def wgrad3(geo, x, cs_in, cin, g, cs_g, cout, gw, gb, variant, workspace):
 
 
 class BlockSpec:
+    """bn, like feed_forward._conv_block's argument: True = BatchNorm + ReLU behind the second convolution, False = the ReLU
+    alone (model_no_batchnorm), None = nothing (the head block)"""
+
     def __init__(self, prefix, cin, cout, bn):
         self.prefix, self.cin, self.cout, self.bn = prefix, cin, cout, bn
 
 
 class Trunk:
-    """Native forward/backward of in_net_hv / in_net_id / out_net for the default flags
-    (BatchNorm on, non-cross) with 2x2 or 3x3 filters.  `params` maps state_dict keys to device tensors.
+    """Native forward/backward of in_net_hv / in_net_id / out_net (non-cross) with 2x2 or 3x3 filters, and, with 2x2
+    filters, with or without BatchNorm (batchnorm=False: model_no_batchnorm, reference feed_forward.py:122-137 -- both ReLUs
+    of a block ride in the convolutions' epilogues, training and inference take the same launches, and the gradient behind a
+    block's trailing ReLU comes out of the data gradient of the convolution above it: _block_fwd_relu, _block_bwd).
+    `params` maps state_dict keys to device tensors.
     ksize 3 runs the exact-f32 3x3 kernels (conv3 / wgrad3): filters packed per layer, BatchNorm statistics by
     mmlf_bn_stats_train, the data gradient's ReLU by `ref`, inference with BatchNorm folded into conv2."""
 
-    def __init__(self, chs, in_blocks, out_blocks, views, oc, momentum, eps=1e-5, ksize=2):
+    def __init__(self, chs, in_blocks, out_blocks, views, oc, momentum, eps=1e-5, ksize=2, batchnorm=True):
         if ksize not in (2, 3):
             raise ValueError(f'native trunk: ksize {ksize} (2 or 3)')
+        if not batchnorm and ksize != 2:
+            raise ValueError('native trunk: blocks without BatchNorm run on the 2x2 kernels only')
+        self.batchnorm = bn = bool(batchnorm)
         self.ksize = ksize
         self.chs, self.views, self.oc = chs, views, oc
         self.momentum, self.eps = float(momentum), float(eps)
@@ -455,12 +477,12 @@ class Trunk:
         self.streams = []
         for key, net, var in (('h', 'in_net_hv', VAR_TRANSPOSE), ('v', 'in_net_hv', VAR_IDENTITY),
                               ('i', 'in_net_id', VAR_TRANSPOSE_FLIPH), ('d', 'in_net_id', VAR_IDENTITY)):
-            blocks = [BlockSpec(f'{net}.0', cin0, chs, True)]
-            blocks += [BlockSpec(f'{net}.{k}', chs, chs, True) for k in range(1, in_blocks)]
+            blocks = [BlockSpec(f'{net}.0', cin0, chs, bn)]
+            blocks += [BlockSpec(f'{net}.{k}', chs, chs, bn) for k in range(1, in_blocks)]
             self.streams.append((key, var, blocks))
         c = 4 * chs
-        self.out_blocks = [BlockSpec(f'out_net.{k}', c, c, True) for k in range(out_blocks - 1)]
-        self.out_blocks.append(BlockSpec(f'out_net.{out_blocks - 1}', c, oc, False))
+        self.out_blocks = [BlockSpec(f'out_net.{k}', c, c, bn) for k in range(out_blocks - 1)]
+        self.out_blocks.append(BlockSpec(f'out_net.{out_blocks - 1}', c, oc, None))
         if chs % 2 or cs_of(c) != c:
             raise ValueError('native trunk needs an even model_chs with 4*model_chs a multiple of 8')
 
@@ -594,6 +616,42 @@ class Trunk:
             rec_list.append(rec)
         return out, cs_out
 
+    def _block_fwd_relu(self, geo, spec, var, x, cs_x, x_relu, xmask, p, rec_list, out=None, cs_out=None, c_off=0, packs=None):
+        """A block without BatchNorm: conv(pad 1) -> ReLU -> conv(pad 0) -> ReLU, both ReLUs in the convolutions' epilogues.
+        out (a stream's last block): the second convolution writes the channel slice [c_off, c_off + cout) of the concat
+        buffer.  x_relu: x is the output of such a block, xmask: the bits of that ReLU if it left any (kept for backward).
+        Returns (output grid tensor, its channel stride, the bits of its ReLU mask or None)."""
+        dev = x.device
+        H, W, P = geo.H, geo.W, geo.P
+        C, cs_mid = spec.cout, cs_of(spec.cout)
+        w1, b1 = p[f'{spec.prefix}.0.weight'], p[f'{spec.prefix}.0.bias']
+        w2, b2 = p[f'{spec.prefix}.2.weight'], p[f'{spec.prefix}.2.bias']
+        packs = packs or {}
+        # (never the matrix-vector kernels: cout is chs >= 2 with cin = 3 views or chs, or 4 chs >= 8; the head is _block_fwd's)
+        pk1 = packs.get((f'{spec.prefix}.0.weight', var, False))
+        if pk1 is None:
+            pk1 = pack_filter(w1, var, False)
+        pk2 = packs.get((f'{spec.prefix}.2.weight', var, False))
+        if pk2 is None:
+            pk2 = pack_filter(w2, var, False)
+        new_out = out is None
+        got = geo.bufs([cs_mid] * (2 if new_out else 1), dev)
+        y = got[0]
+        if new_out:
+            out, cs_out, c_off = got[1], cs_mid, 0
+        bits = rec_list is not None and CONV_MODE == 'f16x3'
+        ymask = geo.relu_mask(dev) if bits else None
+        # the mask of the block's output is read by the data gradient of the NEXT block's first convolution (_block_bwd):
+        # a slice of the concat buffer has no such consumer (mmlf_relu_bwd_slice reads the activations)
+        omask = geo.relu_mask(dev) if bits and new_out else None
+        conv(geo, x, cs_x, spec.cin, pk1, b1, C, y, cs_mid, 0, H + 1, W + 1, True, mask_out=ymask)
+        conv(geo, y, cs_mid, C, pk2, b2, C, out, cs_out, P + 1, H, W, True, n_store=cs_out if new_out else C, out_off=c_off,
+             mask_out=omask)
+        if rec_list is not None:
+            rec_list.append({'spec': spec, 'var': var, 'x': x, 'cs_x': cs_x, 'y': y, 'z': None, 'ymask': ymask,
+                             'x_relu': x_relu, 'xmask': xmask})
+        return out, cs_out, omask
+
     def forward(self, p, stacks, train, save, packed=None):
         """stacks: four (B, views, 3, H, W) contiguous float32 device tensors.
         packed (instead of stacks): (Geometry, [four grid tensors of channel stride cs_of(3 views), with their amax arrays]) --
@@ -629,8 +687,14 @@ class Trunk:
                 call('mmlf_pack_nchw', ptr(stacks[s]), cin0, ptr(x), cs_of(cin0), B, H, W, ptr(x.absmax), _lib.stream_ptr())
             cs_x = cs_of(cin0)
             recs = []
+            xmask = None
             for k, spec in enumerate(blocks):
                 last = k == len(blocks) - 1
+                if spec.bn is False:
+                    x, cs_x, xmask = self._block_fwd_relu(geo, spec, var, x, cs_x, k > 0, xmask, p, recs if save else None,
+                                                          out=concat if last else None, cs_out=4 * self.chs,
+                                                          c_off=s * self.chs, packs=packs)
+                    continue
                 x, cs_x = self._block_fwd(geo, spec, var, x, cs_x, p, train, recs if save else None,
                                           out=concat if last else None, cs_out=4 * self.chs, c_off=s * self.chs, packs=packs,
                                           tracked=tracked, deferred=deferred if last else None)
@@ -643,10 +707,22 @@ class Trunk:
             call('mmlf_bn_apply_relu4', arr(0), cs_of(self.chs), self.chs, arr(1), arr(2), ptr(concat), 4 * self.chs,
                  B, H, W, ptr(concat.absmax), _lib.stream_ptr())
             del deferred[:]
+        if save and not self.batchnorm:
+            tape['concat'] = concat
         x, cs_x = concat, 4 * self.chs
-        for spec in self.out_blocks:
+        xmask = None
+        for k, spec in enumerate(self.out_blocks):
+            if spec.bn is False:
+                # (k == 0: x is the concat buffer, whose ReLU mmlf_relu_bwd_slice applies per stream in backward)
+                x, cs_x, xmask = self._block_fwd_relu(geo, spec, VAR_IDENTITY, x, cs_x, k > 0, xmask, p,
+                                                      tape['out'] if save else None, packs=packs)
+                continue
+            x_in = x
             x, cs_x = self._block_fwd(geo, spec, VAR_IDENTITY, x, cs_x, p, train, tape['out'] if save else None, packs=packs,
                                       tracked=tracked)
+            if save and not self.batchnorm and k > 0:      # the head behind a block without BatchNorm
+                assert tape['out'][-1]['x'] is x_in
+                tape['out'][-1].update(x_relu=True, xmask=xmask)
             if not save:
                 del tape['out'][:]
         if tracked:
@@ -682,6 +758,16 @@ class Trunk:
         def packed(name, w):
             pk = packs.get((name, var, True))
             return pk if pk is not None else (pack_filter3 if k3 else pack_filter)(w, var, True)
+
+        # x is the output of a block without BatchNorm: the data gradient of conv1 applies that block's trailing ReLU, so what
+        # comes out is already the gradient behind it (dz of the block underneath) and costs no pass of its own.  In the f16
+        # split the mask comes as the bits the producing conv2 launch left: that launch and this one have the same (B, H, W),
+        # the same N (the block's width), out_shift P + 1 and a buffer of channel stride cs_x of their own, so they run the same
+        # kernel and epilogue orientation and agree on the private word layout.  Otherwise x itself is the reference.
+        x_relu = {}
+        if rec.get('x_relu'):
+            x_relu = ({'mask_in': rec['xmask']} if rec.get('xmask') is not None and CONV_MODE == 'f16x3'
+                      else {'ref': x, 'cs_ref': cs_x})
 
         # this block's gradient buffers, one zeroing launch: dz (behind BatchNorm), dy, dx
         got = geo.bufs(([cs_mid] if spec.bn else []) + [cs_mid] + ([cs_x] if need_dx else []), dev)
@@ -726,7 +812,7 @@ class Trunk:
         # conv1 (pad 1)
         if overlap and need_dx:
             pk = packed(f'{pre}.0.weight', w1)
-            conv(geo, dy, cs_mid, C, pk, None, spec.cin, dx, cs_x, P + 1, H, W, False)
+            conv(geo, dy, cs_mid, C, pk, None, spec.cin, dx, cs_x, P + 1, H, W, False, **x_relu)
             main = torch.cuda.current_stream()
             ready = main.record_event()
             with torch.cuda.stream(ws.side):
@@ -742,7 +828,7 @@ class Trunk:
         if not need_dx:
             return None
         pk = packed(f'{pre}.0.weight', w1)
-        conv(geo, dy, cs_mid, C, pk, None, spec.cin, dx, cs_x, P + 1, H, W, False)
+        conv(geo, dy, cs_mid, C, pk, None, spec.cin, dx, cs_x, P + 1, H, W, False, **x_relu)
         return dx
 
     def backward(self, p, tape, grad_output, grads, on_done=None):
@@ -789,6 +875,11 @@ class Trunk:
             if s == 2:
                 settle()                    # out_net.0's weight gradient ran beside the first stream's BatchNorm kernels
             gs, cs_s, off = g, cs_g, s * self.chs
+            if not self.batchnorm:
+                # the stream's last ReLU wrote its slice of the concat buffer: the gradient behind it, as a compact tensor
+                cs_s, off = cs_of(self.chs), 0
+                gs = geo.buf(cs_s, dev)
+                relu_bwd_slice(geo, g, cs_g, s * self.chs, tape['concat'], cs_g, s * self.chs, self.chs, gs, cs_s)
             while recs:
                 rec = recs.pop()
                 gs = self._block_bwd(geo, rec, p, grads, gs, cs_s, off, need_dx=bool(recs), packs=tape.get('packs'))

@@ -4,12 +4,13 @@ Same constructor keywords, same ``forward(h_views, v_views, i_views, d_views)`` 
 five-key output dict and the same ``state_dict`` key set, so reference
 checkpoints load unchanged and the reference's train / validate drivers can use it as is.
 
-On CUDA (= HIP on ROCm) tensors with the default flags (BatchNorm, four streams) and model_ksize 2 or 3 the
-whole trunk runs in hand-written gfx950 kernels through the C ABI (engine.Trunk; 3x3 filters on the exact-f32
-kernels whatever MMLF_CONV_MODE says); there is no fallback on that path: a missing libmmlf_hip.so raises.
-CPU tensors, and the flags the README recipes never use (model_cross, other kernel sizes, model_no_batchnorm,
-model_unet), run the module tree with stock torch ops ("plumbing path": BASELINE.json configs[0], CPU tests,
-gloo rehearsal).
+On CUDA (= HIP on ROCm) tensors with four streams and model_ksize 2 or 3 the whole trunk runs in hand-written gfx950
+kernels through the C ABI (engine.Trunk; 3x3 filters on the exact-f32 kernels whatever MMLF_CONV_MODE says), with
+BatchNorm (the default) and, for model_ksize 2, also under model_no_batchnorm (ReLU-only blocks: both ReLUs in the
+convolutions' epilogues, no BatchNorm launch); there is no fallback on that path: a missing libmmlf_hip.so raises.
+CPU tensors, and the flags the README recipes never use (model_cross, other kernel sizes, model_no_batchnorm together
+with model_ksize 3, model_unet), run the module tree with stock torch ops ("plumbing path": BASELINE.json configs[0],
+CPU tests, gloo rehearsal).
 """
 import numpy as np
 import torch
@@ -220,10 +221,10 @@ class FeedForward(nn.Module):
         self.out_chs = oc
         self.unet = bool(model_unet)
 
-        self._native_ok = (not model_unet and model_ksize in (2, 3) and not model_cross and bn and model_chs % 2 == 0
-                           and (4 * model_chs) % 8 == 0 and 4 * model_chs <= 288 and oc <= 288)
+        self._native_ok = (not model_unet and model_ksize in (2, 3) and not model_cross and (bn or model_ksize == 2)
+                           and model_chs % 2 == 0 and (4 * model_chs) % 8 == 0 and 4 * model_chs <= 288 and oc <= 288)
         self._trunk = (Trunk(model_chs, model_in_blocks, model_out_blocks, model_views, oc,
-                             model_batchnorm_momentum, ksize=model_ksize) if self._native_ok else None)
+                             model_batchnorm_momentum, ksize=model_ksize, batchnorm=bn) if self._native_ok else None)
         self._param_names = [n for n, _ in self.named_parameters()]
         self._grids = {}
 

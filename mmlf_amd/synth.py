@@ -24,8 +24,9 @@ def out_channels(model_uncert=False, model_discrete=False, model_views=9,
 
 
 def param_spec(model_chs=70, model_in_blocks=3, model_out_blocks=8, model_views=9,
-               model_uncert=False, model_discrete=False, model_cross=False, **_):
-    """Ordered list of (state_dict key, shape, kind) for the default (k=2, BN) net.
+               model_uncert=False, model_discrete=False, model_cross=False, model_no_batchnorm=False, **_):
+    """Ordered list of (state_dict key, shape, kind) for the k=2 net: with BatchNorm (the default), or, under
+    model_no_batchnorm, without any `.3.*` entry (reference feed_forward.py:122-137).
 
     kind in {'conv_w', 'conv_b', 'bn_w', 'bn_b', 'bn_rm', 'bn_rv', 'bn_nbt'}.
     Order equals torch's ``state_dict()`` order of the reference module tree.
@@ -33,7 +34,7 @@ def param_spec(model_chs=70, model_in_blocks=3, model_out_blocks=8, model_views=
     oc = out_channels(model_uncert, model_discrete, model_views, model_cross)
     spec = []
 
-    def block(prefix, cin, cout, bn=True):
+    def block(prefix, cin, cout, bn=not model_no_batchnorm):
         spec.append((f'{prefix}.0.weight', (cout, cin, 2, 2), 'conv_w'))
         spec.append((f'{prefix}.0.bias', (cout,), 'conv_b'))
         spec.append((f'{prefix}.2.weight', (cout, cout, 2, 2), 'conv_w'))
