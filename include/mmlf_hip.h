@@ -310,7 +310,8 @@ int mmlf_fold_bn_eval3x3(const float *w_oihw, const float *bias, const float *sc
 int mmlf_audit_conv3x3(int cs_in, int K, int N, int cs_out, int N_store, int cs_ref, int B, int H, int W, int64_t *ends);
 int mmlf_audit_wgrad3x3(int cs_in, int Cin, int cs_g, int Cout, int B, int H, int W, int64_t *ends);
 
-/* UPR head (feed_forward.py:292-302, laplacian :9-12): posterior[b,k,y,x] from output[:,0:2]. */
+/* UPR head (feed_forward.py:292-302, laplacian :9-12): posterior[b,k,y,x] from output[:,0:2].  The head and loss entry
+ * points below refuse B, H or W <= 0 (nothing is launched). */
 int mmlf_head_upr(const float *output_nchw, const float *grid108, float *posterior, int steps,
                   int B, int H, int W, void *stream);
 /* DPP head (feed_forward.py:276-290, dl.py:160-182). */

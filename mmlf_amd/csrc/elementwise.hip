@@ -1658,6 +1658,7 @@ extern "C" int mmlf_head_upr(const float *output, const float *grid108, float *p
                              int W, void *stream)
 {
     MMLF_CHECK_ARG(output && grid108 && posterior && steps > 0, "mmlf_head_upr: bad argument");
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_head_upr: B=%d H=%d W=%d", B, H, W);
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(head_upr_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, output, grid108,
                        posterior, steps, H * W, total);
@@ -1670,6 +1671,7 @@ extern "C" int mmlf_head_dpp(const float *scores, const float *grid_torch, const
 {
     MMLF_CHECK_ARG(scores && grid_torch && grid_np && one_hot && posterior && mean && logvar && steps > 0,
                    "mmlf_head_dpp: bad argument");
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_head_dpp: B=%d H=%d W=%d", B, H, W);
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(head_dpp_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, scores, grid_torch,
                        grid_np, one_hot, posterior, mean, logvar, steps, H * W, total);
@@ -1680,6 +1682,7 @@ extern "C" int mmlf_head_upr_bwd(const float *output, const float *grid108, cons
                                  int steps, int B, int H, int W, void *stream)
 {
     MMLF_CHECK_ARG(output && grid108 && grad_posterior && grad_output && steps > 0, "mmlf_head_upr_bwd: bad argument");
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_head_upr_bwd: B=%d H=%d W=%d", B, H, W);
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(head_upr_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, output, grid108,
                        grad_posterior, grad_output, steps, H * W, total);
@@ -1691,6 +1694,7 @@ extern "C" int mmlf_head_dpp_bwd(const float *scores, const float *grid_np, cons
 {
     MMLF_CHECK_ARG(scores && grid_np && mean && grad_scores && steps > 0 && (grad_posterior || grad_logvar),
                    "mmlf_head_dpp_bwd: bad argument");
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_head_dpp_bwd: B=%d H=%d W=%d", B, H, W);
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(head_dpp_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, scores, grid_np, mean,
                        grad_posterior, grad_logvar, grad_scores, steps, H * W, total);
@@ -1707,6 +1711,7 @@ extern "C" int mmlf_loss_fwd_bwd(int kind, const float *output, int oc, const fl
     MMLF_CHECK_ARG((kind == 0 && oc >= 1) || (kind == 1 && oc >= 2) || (kind == 2 && grid_torch && oc >= 1),
                    "mmlf_loss_fwd_bwd: oc=%d for kind=%d", oc, kind);
     MMLF_CHECK_ARG(nblocks > 0 && nblocks <= 4096, "mmlf_loss_fwd_bwd: nblocks=%d", nblocks);
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_loss_fwd_bwd: B=%d H=%d W=%d", B, H, W);
     const long long total = (long long)B * H * W;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(loss_partial_kernel, dim3(nblocks), dim3(256), 0, st, kind, output, oc, gt, mask, grid_torch,

@@ -25,7 +25,7 @@ import ctypes
 import pytest
 import torch
 
-from tests_helpers import bn_apply_ref, bn_bwd_ref, bn_stats_ref
+from tests_helpers import RATIOS, _Pool, _bar, _ints, _pick, _same, _ulp, bn_apply_ref, bn_bwd_ref, bn_stats_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -52,11 +52,10 @@ COEFFS_C = [1, 63, 64, 65, 280]
 SLACK_FRAMES = [(1, 1, 1), (2, 29, 1), (2, 3, 300)]
 BN_BLOCKS = 1024
 
-SENT, GUARDVAL, JUNK, NGUARD = 1234.5, -4321.0, 777.25, 64
+SENT, JUNK = 1234.5, 777.25
 NAN = float('nan')
 E23, E22, E24 = 2.0 ** -23, 2.0 ** -22, 2.0 ** -24
 DYADIC = (-0.5, -0.25, 0.25, 0.5, 1.0, 2.0)
-RATIOS = {}                                  # bar -> largest error / bar seen (printed when the module is done)
 
 
 def _dev():
@@ -70,39 +69,7 @@ def _report_ratios():
     for k in sorted(RATIOS):
         print(f'\n[elementwise headroom] {k}: max error / bar = {RATIOS[k]:.4f}', end='')
     print()
-
-
-class _Pool:
-    """output buffers between guard bands"""
-
-    def __init__(self, dev):
-        self.dev, self.items = dev, []
-
-    def new(self, n, fill, dtype=torch.float32):
-        full = torch.full((n + 2 * NGUARD,), GUARDVAL, dtype=dtype, device=self.dev)
-        inner = full[NGUARD:NGUARD + n]
-        inner.fill_(fill)
-        self.items.append((full, n))
-        return inner
-
-    def of(self, t):
-        inner = self.new(t.numel(), 0.0, t.dtype)
-        inner.copy_(t.reshape(-1))
-        return inner
-
-    def check(self, what):
-        for k, (full, n) in enumerate(self.items):
-            assert bool((full[:NGUARD] == GUARDVAL).all()) and bool((full[NGUARD + n:] == GUARDVAL).all()), \
-                (what, f'guard band of buffer {k} ({n} elements) overwritten')
-
-
-def _pick(values, shape, gen):
-    v = torch.tensor(values, dtype=torch.float32, device=gen.device)
-    return v[torch.randint(0, len(values), shape, device=gen.device, generator=gen)]
-
-
-def _ints(lo, hi, shape, gen):
-    return torch.randint(lo, hi + 1, shape, device=gen.device, generator=gen).float()
+    RATIOS.clear()                               # the table is shared with the other modules that use _bar
 
 
 def _normal(shape, gen, standardize):
@@ -115,33 +82,6 @@ def _normal(shape, gen, standardize):
         flat = (flat - flat.mean(0)) / flat.var(0, unbiased=False).sqrt().clamp_min(1e-3)
         r = flat.reshape(shape)
     return r
-
-
-def _bar(err, bar, key, what):
-    """err <= bar element-wise (a NaN fails); the largest ratio is kept for the headroom report"""
-    ratio = err / bar.clamp_min(1e-300)
-    worst = float(ratio.max()) if ratio.numel() else 0.0
-    RATIOS[key] = max(RATIOS.get(key, 0.0), worst if worst == worst else float('inf'))
-    ok = err <= bar
-    assert bool(ok.all()), (what, key, f'{int((~ok).sum())} of {ok.numel()} over the bar, worst ratio {worst}',
-                            f'first at flat index {int((~ok).reshape(-1).to(torch.uint8).argmax())}')
-
-
-def _ulp(got, ref, key, what, ulps=1.0):
-    """|got - ref| <= ulps float32 units in the last place (of the larger of the two magnitudes)"""
-    g = got.double()
-    mag = torch.maximum(g.abs(), ref.abs()).clamp_min(2.0 ** -126)
-    _bar((g - ref).abs(), ulps * torch.exp2(torch.floor(torch.log2(mag)) - 23), key, what)
-
-
-def _same(got, want, what):
-    """equal values, element for element (float32 against the float64 reference, which must itself be a float32 number)"""
-    assert bool((want.float().double() == want).all()), (what, 'precondition: the exact result is a float32 number')
-    bad = ~(got.double() == want)
-    if bool(bad.any()):
-        k = int(bad.reshape(-1).to(torch.uint8).argmax())
-        raise AssertionError(f'{what}: {int(bad.sum())} of {bad.numel()} elements differ from the exact result; flat index {k} '
-                             f'holds {float(got.reshape(-1)[k])!r}, exact {float(want.reshape(-1)[k])!r}')
 
 
 def _all_equal(got, exp, cs, what):

@@ -1,5 +1,6 @@
 """Small numpy helpers shared by the GPU parity tests."""
 import numpy as np
+import torch
 
 
 def _master(dy, dx, variant):
@@ -208,3 +209,259 @@ def bn_bwd_ref(zg, gyg, scale, shift, gamma, mean, invstd):
     return BnBwd(mask=mask, dgamma=dgamma, dbeta=dbeta, k1=k1, k2=k2, k3=k3, dz=k1 * g - k2 - k3 * zc,
                  sum_abs_g=g.abs().sum((0, 1, 2)), sum_abs_gz=(g.abs() * zhat.abs()).sum((0, 1, 2)),
                  dz_abs=(k1 * g).abs() + k2.abs() + k3.abs() * zc.abs())
+
+
+# ------------------------------------------------------------------ helpers of the direct-call GPU modules
+# (tests/test_gpu_elementwise.py, tests/test_gpu_losses.py, tests/test_gpu_heads.py)
+GUARDVAL, NGUARD = -4321.0, 64
+RATIOS = {}                                  # bar -> largest error / bar seen (each module prints and clears it when done)
+
+
+class _Pool:
+    """output buffers between guard bands"""
+
+    def __init__(self, dev):
+        self.dev, self.items = dev, []
+
+    def new(self, n, fill, dtype=torch.float32):
+        full = torch.full((n + 2 * NGUARD,), GUARDVAL, dtype=dtype, device=self.dev)
+        inner = full[NGUARD:NGUARD + n]
+        inner.fill_(fill)
+        self.items.append((full, n))
+        return inner
+
+    def of(self, t):
+        inner = self.new(t.numel(), 0.0, t.dtype)
+        inner.copy_(t.reshape(-1))
+        return inner
+
+    def check(self, what):
+        for k, (full, n) in enumerate(self.items):
+            assert bool((full[:NGUARD] == GUARDVAL).all()) and bool((full[NGUARD + n:] == GUARDVAL).all()), \
+                (what, f'guard band of buffer {k} ({n} elements) overwritten')
+
+
+def _pick(values, shape, gen):
+    v = torch.tensor(values, dtype=torch.float32, device=gen.device)
+    return v[torch.randint(0, len(values), shape, device=gen.device, generator=gen)]
+
+
+def _ints(lo, hi, shape, gen):
+    return torch.randint(lo, hi + 1, shape, device=gen.device, generator=gen).float()
+
+
+def _bar(err, bar, key, what):
+    """err <= bar element-wise (a NaN fails); the largest ratio is kept for the headroom report"""
+    ratio = err / bar.clamp_min(1e-300)
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    RATIOS[key] = max(RATIOS.get(key, 0.0), worst if worst == worst else float('inf'))
+    ok = err <= bar
+    assert bool(ok.all()), (what, key, f'{int((~ok).sum())} of {ok.numel()} over the bar, worst ratio {worst}',
+                            f'first at flat index {int((~ok).reshape(-1).to(torch.uint8).argmax())}')
+
+
+def _ulp(got, ref, key, what, ulps=1.0):
+    """|got - ref| <= ulps float32 units in the last place (of the larger of the two magnitudes)"""
+    g = got.double()
+    mag = torch.maximum(g.abs(), ref.abs()).clamp_min(2.0 ** -126)
+    _bar((g - ref).abs(), ulps * torch.exp2(torch.floor(torch.log2(mag)) - 23), key, what)
+
+
+def _same(got, want, what):
+    """equal values, element for element (float32 against the float64 reference, which must itself be a float32 number)"""
+    assert bool((want.float().double() == want).all()), (what, 'precondition: the exact result is a float32 number')
+    bad = ~(got.double() == want)
+    if bool(bad.any()):
+        k = int(bad.reshape(-1).to(torch.uint8).argmax())
+        raise AssertionError(f'{what}: {int(bad.sum())} of {bad.numel()} elements differ from the exact result; flat index {k} '
+                             f'holds {float(got.reshape(-1)[k])!r}, exact {float(want.reshape(-1)[k])!r}')
+
+
+def _close(got, ref, bar, key, what):
+    """|got - ref| <= bar wherever the reference is finite; where it is not (the documented NaN of loss kind 4, the -inf logvar
+    of the DPP head) `got` must be the same non-finite value.  No element is left out."""
+    g = got.double().reshape(ref.shape)
+    fin = torch.isfinite(ref)
+    same = (g == ref) | (torch.isnan(g) & torch.isnan(ref))
+    assert bool(same[~fin].all()), (what, key, 'differs from the non-finite value of the reference')
+    assert bool(torch.isfinite(bar[fin]).all()), (what, key, 'precondition: a finite bar wherever the reference is finite')
+    zero = torch.zeros_like(ref)
+    _bar(torch.where(fin, (g - ref).abs(), zero), torch.where(fin, bar, zero), key, what)
+
+
+# ------------------------------------------------------------------ losses, heads and Adam: float64 references
+# Plain torch expressions of the mathematics, in float64, on whatever device the operands have.  The operands arrive as the
+# float32 tensors the kernels read.  DECISIONS the kernels specify as float32 expressions are taken here from the same float32
+# torch expression, and everything after the decision is float64:
+#   * |grid_k - gt| < half_step: a float32 subtraction against the float32 half_step;
+#   * tot < 0.01f on the sequential float32 sum of the alphas (loss_ref asserts that every total lies outside [0.005, 0.02]
+#     or is a float32 sum that equals the float64 one exactly, so the float64 sum the mathematics uses agrees);
+#   * raw > 0 and v == max: the same in either precision;
+#   * the sign of a float32 difference.
+class Ref:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _sign32(a, b):
+    """sign of the float32 difference a - b, as float64 (0 where they are equal)"""
+    return torch.sign(a.float() - b.float()).double()
+
+
+def _bins32(grid, x, half_step):
+    """[|grid_k - x| < half_step] in float32: grid (K,), x (B, ..., H, W) -> (B, K, ..., H, W) float64"""
+    g = grid.float().view(1, -1, *([1] * (x.dim() - 1)))
+    half = torch.tensor(half_step, dtype=torch.float64).float().to(x.device)
+    return (torch.abs(g - x.float().unsqueeze(1)) < half).double()
+
+
+def loss_ref(kind, out, target, mask, mask_padding=None, grid=None, half_step=0.0, den_override=None, aux_override=None):
+    """The seven training losses on the raw output `out` (B, oc, H, W), float32: 0 masked L1, 1 Laplace NLL (mean, logvar),
+    2 cross entropy on relu(scores) against the one-hot of gt, 3 alpha-weighted L1 to every plane of target (B, P, 5, H, W),
+    4 its Laplace NLL normalised by the mean total alpha with a -logvar term on pixels without a surface, 5 cross entropy
+    against the alpha-weighted more-hot target, 6 the Laplace NLL with mask_padding.  loss = sum(l mask) / den with
+    den = den_override, or the number of mask pixels, or 1 where that is 0; aux_override = (s0, s1) replaces the whole-batch
+    sums of kind 4 (sum of the total alpha, number of surface-less pixels) and kind 6 (number of in-range pixels, unused).
+    Returns Ref(l, g, loss, grad, count, sum, den, aux, parts): l (B, H, W) the per-pixel loss, g (B, c, H, W) its derivative
+    with respect to the channels the loss uses, grad = g mask / den, parts the absolute terms the rounding bars are built of."""
+    o = out.double()
+    B, oc, H, W = o.shape
+    n = B * H * W
+    mk = mask.double()
+    parts, aux = {}, None
+    if kind in (0, 1, 6):
+        d, s = (o[:, 0] - target.double()).abs(), _sign32(out[:, 0], target)
+    if kind == 0:
+        l, g = d, s.unsqueeze(1)
+    elif kind == 1:
+        lv = o[:, 1]
+        e = torch.exp(-lv)
+        l, g = e * d + lv, torch.stack([e * s, 1 - e * d], 1)
+        parts = dict(ed=e * d)
+    elif kind in (2, 5):
+        if kind == 2:
+            t = _bins32(grid, target, half_step)
+        else:
+            t = (_bins32(grid, target[:, :, 4], half_step) * target[:, :, 3].double().unsqueeze(1)).sum(2)
+        v = o.clamp_min(0)
+        dot, z = (v * t).sum(1), torch.exp(v).sum(1)
+        l = -torch.log(torch.exp(dot) / z)
+        pk = torch.exp(o) / z.unsqueeze(1)
+        g = torch.where(out > 0, pk - t, torch.zeros_like(pk))
+        parts = dict(dot=dot, pk=pk, t=t)
+    elif kind in (3, 4):
+        w, tg = target[:, :, 3].double(), target[:, :, 4].double()
+        d, s = (o[:, 0].unsqueeze(1) - tg).abs(), _sign32(out[:, 0].unsqueeze(1), target[:, :, 4])
+        if kind == 3:
+            l, g = (d * w).sum(1), (s * w).sum(1, keepdim=True)
+            parts = dict(sw=w.abs().sum(1))
+        else:
+            lv = o[:, 1]
+            e = torch.exp(-lv)
+            tot32 = torch.zeros_like(target[:, 0, 3])
+            for k in range(target.shape[1]):
+                tot32 = tot32 + target[:, k, 3]
+            tot = w.sum(1)
+            assert bool(((tot < 0.005) | (tot > 0.02) | (tot32.double() == tot)).all()), \
+                'precondition: a total alpha in [0.005, 0.02] whose float32 sum is not exact'
+            oor = (tot32 < torch.tensor(0.01, dtype=torch.float32)).double()
+            s0, s1 = (tot.sum(), oor.sum()) if aux_override is None else (aux_override[0].double(), aux_override[1].double())
+            aux = (s0, s1)
+            f0, f1 = s0 / n, n / s1                          # f1 = inf where no pixel lacks a surface: 0 * inf = NaN below
+            term = (e.unsqueeze(1) * d + lv.unsqueeze(1)) * w
+            acc, gm, glv = term.sum(1), (e.unsqueeze(1) * s * w).sum(1), ((1 - e.unsqueeze(1) * d) * w).sum(1)
+            l_oor = -lv * oor * f1
+            l = (acc / f0 + l_oor) / 2
+            g = torch.stack([gm / f0 / 2, (glv / f0 - oor * f1) / 2], 1)
+            parts = dict(sE=(e.unsqueeze(1) * d * w).sum(1), sT=term.abs().sum(1), acc=acc, f0=f0, f1=f1, l_oor=l_oor,
+                         sew=(e.unsqueeze(1) * w).sum(1), sG=((1 - e.unsqueeze(1) * d).abs() * w).sum(1), glv=glv, oor=oor)
+    else:
+        lv = o[:, 1]
+        e = torch.exp(-lv)
+        mp = mask_padding.double()
+        oor = 1 - mp
+        s0 = mp.sum() if aux_override is None else aux_override[0].double()
+        aux = (s0, None)
+        f0 = n / s0 if float(s0) > 0 else torch.ones_like(s0)
+        f1 = n / (n - s0) if float(n - s0) > 0 else torch.ones_like(s0)
+        l_in, l_oor = (e * d + lv) * mp * f0, -lv * oor * f1
+        l = (l_in + l_oor) / 2
+        g = torch.stack([e * s * mp * f0 / 2, ((1 - e * d) * mp * f0 - oor * f1) / 2], 1)
+        parts = dict(ed=e * d, f0=f0, f1=f1, mp=mp, oor=oor, l_in=l_in, l_oor=l_oor, nll=e * d + lv)
+    count = mk.sum()
+    den = count if den_override is None else den_override.double().reshape(())
+    den_used = torch.where(den == 0, torch.ones_like(den), den)
+    total = (l * mk).sum()
+    return Ref(l=l, g=g, loss=total / den_used, grad=g * (mk / den_used).unsqueeze(1), count=count, den=den, den_used=den_used,
+               sum=total, aux=aux, parts=parts)
+
+
+def upr_ref(out, grid, grad_posterior=None):
+    """The UPR head: posterior_k = exp(-|grid_k - mu| / b) / (2 b), b = exp(logvar), on out (B, 2, H, W); with grad_posterior
+    (B, K, H, W) also the gradient with respect to out: d post_k / d mu = post_k sign(grid_k - mu) / b (0 where they are
+    equal), d post_k / d logvar = post_k (|grid_k - mu| / b - 1).  Returns Ref(post, gout, t, b, tm, tl): t = |grid_k - mu| / b,
+    tm / tl the per-bin terms of the two sums."""
+    o = out.double()
+    mu, b = o[:, 0].unsqueeze(1), torch.exp(o[:, 1]).unsqueeze(1)
+    gk = grid.double().view(1, -1, 1, 1)
+    t = (gk - mu).abs() / b
+    post = 1.0 / (2.0 * b) * torch.exp(-t)
+    r = Ref(post=post, t=t, b=b, gout=None)
+    if grad_posterior is not None:
+        go = grad_posterior.double()
+        s = _sign32(grid.view(1, -1, 1, 1), out[:, 0].unsqueeze(1))
+        r.tm, r.tl = go * post * s / b, go * post * (t - 1)
+        r.gout = torch.stack([r.tm.sum(1), r.tl.sum(1)], 1)
+    return r
+
+
+def dpp_ref(scores, grid_torch, grid_np):
+    """The DPP head on scores (B, K, H, W): one_hot = [s == max s] (every maximum), posterior = softmax, mean =
+    sum grid_torch one_hot, logvar = log sum (grid_np - mean)^2 posterior (-inf where the posterior sits on the arg-max bin
+    alone)."""
+    s = scores.double()
+    one_hot = (torch.max(s, 1, keepdim=True)[0] == s).double()
+    e = torch.exp(s)
+    post = e / e.sum(1, keepdim=True)
+    mean = (grid_torch.double().view(1, -1, 1, 1) * one_hot).sum(1)
+    d = grid_np.double().view(1, -1, 1, 1) - mean.unsqueeze(1)
+    V = (d * d * post).sum(1)
+    return Ref(one_hot=one_hot, post=post, mean=mean, logvar=torch.log(V), V=V, d=d)
+
+
+def dpp_bwd_ref(scores, grid_np, mean, grad_posterior=None, grad_logvar=None):
+    """Gradient of dpp_ref's posterior and logvar with respect to the scores, `mean` (B, H, W) a constant of the graph:
+    dL/dp_k = grad_posterior_k + grad_logvar (grid_np_k - mean)^2 / V, dL/ds_i = p_i (dL/dp_i - sum_j dL/dp_j p_j); either
+    gradient may be None (it is left out).  Returns Ref(gs, post, d, V, gl, dp, dot)."""
+    s = scores.double()
+    e = torch.exp(s)
+    post = e / e.sum(1, keepdim=True)
+    d = grid_np.double().view(1, -1, 1, 1) - mean.double().unsqueeze(1)
+    V = (d * d * post).sum(1)
+    dp = torch.zeros_like(s) if grad_posterior is None else grad_posterior.double()
+    gl = None
+    if grad_logvar is not None:
+        gl = (grad_logvar.double() / V).unsqueeze(1)
+        dp = dp + gl * d * d
+    dot = (dp * post).sum(1, keepdim=True)
+    return Ref(gs=post * (dp - dot), post=post, d=d, V=V, gl=gl, dp=dp, dot=dot)
+
+
+def adam_ref(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
+    """One step of torch.optim.Adam (no weight decay, no amsgrad) on the gradient g * grad_scale -> (p, m, v)"""
+    gi = g.double() * grad_scale
+    m2 = m.double() + (gi - m.double()) * (1 - beta1)
+    v2 = v.double() * beta2 + gi * gi * (1 - beta2)
+    bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
+    denom = v2.sqrt() / bc2 ** 0.5 + eps
+    return p.double() - lr / bc1 * (m2 / denom), m2, v2
+
+
+# shape lists of tests/test_gpu_losses.py and of the direct-call tests of tests/test_gpu_heads.py (held to their classes by
+# tests/test_loss_head_cpu.py): (B, H, W) with a total of 1 | 255, 256, 257: one block short, exact, one over | B > 1 and an odd
+# HW | two batches of 300; the stride frame: more than 8192 * 256 pixels, so a thread of the capped launch takes a second turn
+LOSS_FRAMES = [(1, 1, 1), (1, 1, 255), (1, 1, 256), (1, 1, 257), (3, 5, 7), (2, 1, 300)]
+LOSS_STRIDE_FRAME = (1, 1024, 2049)
+LOSS_NBLOCKS = [1, 3, 63, 64, 65, 1024, 4096]
+LOSS_NBLOCKS_FRAMES = [(3, 5, 7), (2, 1, 300)]
+ADAM_N = [1, 255, 256, 257, 2097153]
