@@ -5,102 +5,76 @@ RuntimeError is raised (with the text from ``mmlf_last_error()``).
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MMLF_HIP_LIB selects another build of the same ABI (kernel A/B experiments); never a fallback
 LIB_PATH = os.environ.get('MMLF_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libmmlf_hip.so')
 
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-_i64 = ctypes.c_int64
-_d = ctypes.c_double
+_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'mmlf_hip.h')
+_CTYPES = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_longlong,
+           'double': ctypes.c_double, 'float': ctypes.c_float}
 
-# name -> (restype, argtypes); must list every symbol of include/mmlf_hip.h
-SIGNATURES = {
-    'mmlf_last_error': (ctypes.c_char_p, []),
-    'mmlf_abi_version': (_i, []),
-    'mmlf_build_info': (ctypes.c_char_p, []),
-    'mmlf_build_is_ablation': (_i, []),
-    'mmlf_conv_cus': (_i, []),
-    'mmlf_audit_conv_h2': (_i, [_i] * 10 + [_vp]),
-    'mmlf_audit_wgrad_h2': (_i, [_i] * 8 + [_vp]),
-    'mmlf_grid_alloc_positions': (_i64, [_i, _i, _i]),
-    'mmlf_packed_filter_floats': (_i64, [_i, _i]),
-    'mmlf_wgrad_workspace_floats': (_i64, [_i, _i, _i, _i, _i]),
-    'mmlf_pack_filter': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_conv2x2': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    'mmlf_packed_filter_split_bytes': (_i64, [_i, _i]),
-    'mmlf_pack_filter_split': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_conv2x2_split': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    'mmlf_conv2x2_wgrad_h2': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    'mmlf_packed_filter_h2_bytes': (_i64, [_i, _i]),
-    'mmlf_amax_entries': (_i64, [_i, _i, _i]),
-    'mmlf_grid_pad_w': (_i, []),
-    'mmlf_grid_pad_h': (_i, []),
-    'mmlf_amax_head': (_i, []),
-    'mmlf_amax_shard_stride': (_i, []),
-    'mmlf_pack_filter_h2': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_packed_filter_h2_columns': (_i, [_i]),
-    'mmlf_pack_filters_h2': (_i, [_vp, _i, _i, _vp]),
-    'mmlf_conv2x2_h2': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'mmlf_relu_mask_words': (_i64, [_i, _i, _i]),
-    'mmlf_conv2x2_thin_workspace_floats': (_i64, [_i, _i, _i]),
-    'mmlf_conv2x2_thin': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    'mmlf_conv2x2_wgrad_thin_workspace_floats': (_i64, [_i]),
-    'mmlf_conv2x2_wgrad_thin': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
-    'mmlf_conv2x2_blocks': (_i, [_i, _i, _i, _i, _i]),
-    'mmlf_bn_stats_finalize': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    'mmlf_conv2x2_wgrad': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
-    'mmlf_conv2x2_wgrad_split': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
-    'mmlf_bn_stats_train': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_bn_coeffs_eval': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _vp]),
-    'mmlf_fold_bn_eval': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    'mmlf_bn_apply_relu': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    'mmlf_bn_apply_relu4': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    'mmlf_bn_bwd_reduce': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_bn_bwd_apply': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    'mmlf_relu_bwd_slice': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    'mmlf_audit_relu_bwd_slice': (_i, [_i] * 9 + [_vp]),
-    'mmlf_pack_nchw': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    'mmlf_zero_slack': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    'mmlf_zero_slack4': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    'mmlf_unpack_nchw': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_head_upr': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_head_dpp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_head_upr_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_head_dpp_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_loss_fwd_bwd': (_i, [_i, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
-    'mmlf_loss_multi_scratch_doubles': (_i64, [_i]),
-    'mmlf_loss_multi_fwd_bwd': (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
-    'mmlf_adam_step': (_i, [_vp, _vp, _vp, _vp, _i64, _d, _d, _d, _d, _i64, _d, _vp]),
-    'mmlf_shift_views': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_shift_pack': (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    'mmlf_lmm_to_discrete': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
-    'mmlf_patch_gather': (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 12 + [_i, _i, _vp]),
-    'mmlf_patch_contrast': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    'mmlf_ensamble_reduce': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    # 3x3 filters (--model_ksize 3)
-    'mmlf_grid_alloc_positions_k3': (_i64, [_i, _i, _i]),
-    'mmlf_zero_slack_k3': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    'mmlf_zero_slack4_k3': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    'mmlf_packed_filter3x3_floats': (_i64, [_i, _i]),
-    'mmlf_pack_filter3x3': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    'mmlf_conv3x3': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    'mmlf_wgrad3x3_workspace_floats': (_i64, [_i, _i, _i, _i, _i]),
-    'mmlf_conv3x3_wgrad': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
-    'mmlf_fold_bn_eval3x3': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    'mmlf_audit_conv3x3': (_i, [_i] * 9 + [_vp]),
-    'mmlf_audit_wgrad3x3': (_i, [_i] * 7 + [_vp]),
-}
+
+def signatures_from_header(text):
+    """{name: (restype, [argtypes])} of every prototype in a C header written like include/mmlf_hip.h: comments,
+    preprocessor lines, `typedef struct {...} name;` and `enum {...};` are skipped, everything else must be
+    `ret name(params);`.  Any pointer or array declarator is a c_void_p (a `const char *` result a c_char_p), a scalar one
+    of _CTYPES; whatever is not recognised raises with the prototype's text -- a guessed argument type would shift every
+    argument behind it."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    text = re.sub(r'^[ \t]*#(?:[^\n]*\\\n)*[^\n]*', ' ', text, flags=re.M)
+    text = re.sub(r'\btypedef\s+struct\b[^{;]*\{[^{}]*\}[^;]*;', ' ', text)
+    text = re.sub(r'\benum\b[^{;]*\{[^{}]*\}\s*;', ' ', text)
+    text = re.sub(r'\bextern\s+"C"\s*\{', ' ', text).replace('}', ' ')     # (its closing brace stands alone)
+
+    def scalar(words, proto):
+        key = ' '.join(w for w in words.split() if w != 'const')
+        if key not in _CTYPES:
+            raise ValueError(f'C header: unknown type `{words.strip()}` in `{proto}`')
+        return _CTYPES[key]
+
+    sigs = {}
+    for stmt in text.split(';'):
+        proto = ' '.join(stmt.split())
+        if not proto:
+            continue
+        m = re.fullmatch(r'([\w\s\*]+?)\b(\w+) ?\(([^()]*)\)', proto)
+        if m is None or m.group(2) in sigs:
+            raise ValueError(f'C header: cannot parse `{proto}`')
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        if '*' in ret:
+            if ret.split() != ['const', 'char', '*']:
+                raise ValueError(f'C header: unknown return type `{ret.strip()}` in `{proto}`')
+            res = ctypes.c_char_p
+        else:
+            res = scalar(ret, proto)
+        args = []
+        for param in ([] if params == 'void' else params.split(',')):
+            d = re.fullmatch(r'\s*([\w\s\*]*?[\w\*])\s*\b(\w+)\s*((?:\[\w*\])?)\s*', param)
+            if d is None or not re.search(r'\w', d.group(1)):
+                raise ValueError(f'C header: cannot parse parameter `{param.strip()}` of `{proto}`')
+            args.append(ctypes.c_void_p if '*' in d.group(1) or d.group(3) else scalar(d.group(1), proto))
+        sigs[name] = (res, args)
+    return sigs
+
+
+def _header_text():
+    with open(_HEADER) as f:
+        return f.read()
+
+
+# name -> (restype, argtypes) of every entry point: include/mmlf_hip.h is the one place that declares them (the compiler
+# holds the definitions in csrc/ to the same file)
+SIGNATURES = signatures_from_header(_header_text())
+
 
 def _header_abi_version():
     """MMLF_ABI_VERSION as include/mmlf_hip.h defines it: ONE place holds the number (the library returns the same macro)"""
-    import re
-    path = os.path.join(os.path.dirname(_HERE), 'include', 'mmlf_hip.h')
-    with open(path) as f:
-        m = re.search(r'^#define\s+MMLF_ABI_VERSION\s+(\d+)', f.read(), re.M)
+    m = re.search(r'^#define\s+MMLF_ABI_VERSION\s+(\d+)', _header_text(), re.M)
     if m is None:
-        raise RuntimeError(f'{path}: no MMLF_ABI_VERSION')
+        raise RuntimeError(f'{_HEADER}: no MMLF_ABI_VERSION')
     return int(m.group(1))
 
 

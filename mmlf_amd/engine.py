@@ -5,6 +5,7 @@ step is a call through the C ABI (include/mmlf_hip.h).
 
 Layout and indexing are described in include/mmlf_hip.h and DESIGN.md section 3.
 """
+import ctypes
 import os
 import threading
 
@@ -61,7 +62,6 @@ class Geometry:
             t = torch.empty(self.alloc * cs, dtype=torch.float32, device=device)
             t.absmax = torch.empty(self.amax_n, dtype=torch.float32, device=device)
             ts.append(t)
-        import ctypes
         n = len(ts)
         grid = (ctypes.c_void_p * 4)(*([ptr(t) for t in ts] + [None] * (4 - n)))
         amax = (ctypes.c_void_p * 4)(*([ptr(t.absmax) for t in ts] + [None] * (4 - n)))
@@ -205,36 +205,45 @@ class _Workspace:
 # 'f16x3': 2-way f16 split of power-of-two-scaled operands, 3 MFMA passes (f32-equivalent accuracy, 5.3x the
 # f32 MFMA rate); 'bf16x6': 3-way bf16 split, 6 passes (no operand scaling needed); 'f32': exact-f32 MFMA
 CONV_MODE = os.environ.get('MMLF_CONV_MODE', 'f16x3')
+# per mode: the size query of a packed filter, the bytes per unit of its answer (the split forms count bytes, the f32 one
+# floats) and the packing entry point; any other mode string runs the f32 kernels
+_PACK = {'f16x3': ('mmlf_packed_filter_h2_bytes', 1, 'mmlf_pack_filter_h2'),
+         'bf16x6': ('mmlf_packed_filter_split_bytes', 1, 'mmlf_pack_filter_split'),
+         'f32': ('mmlf_packed_filter_floats', 4, 'mmlf_pack_filter')}
+_PACK3 = ('mmlf_packed_filter3x3_floats', 4, 'mmlf_pack_filter3x3')
 
 
-def pack_filter(w, variant, dgrad):
+def _pack(who, query, unit, entry, w, variant, dgrad):
     cout, cin = w.shape[0], w.shape[1]
     K, N = (cout, cin) if dgrad else (cin, cout)
-    if CONV_MODE == 'f16x3':
-        n = int(_lib.load().mmlf_packed_filter_h2_bytes(cs_of(K), N))
-        if n < 0:
-            raise RuntimeError(f'pack_filter: unsupported channels K={K} N={N}')
-        out = torch.empty(n // 4, dtype=torch.float32, device=w.device)
-        call('mmlf_pack_filter_h2', ptr(w), ptr(out), cout, cin, variant, int(dgrad), _lib.stream_ptr())
-        return out
-    if CONV_MODE == 'bf16x6':
-        n = int(_lib.load().mmlf_packed_filter_split_bytes(cs_of(K), N))
-        if n < 0:
-            raise RuntimeError(f'pack_filter: unsupported channels K={K} N={N}')
-        out = torch.empty(n // 4, dtype=torch.float32, device=w.device)
-        call('mmlf_pack_filter_split', ptr(w), ptr(out), cout, cin, variant, int(dgrad), _lib.stream_ptr())
-        return out
-    # the kernel walks K in chunks of 8 over the channel stride of its input
-    n = int(_lib.load().mmlf_packed_filter_floats(cs_of(K), N))
+    # the kernels walk K in chunks of 8 over the channel stride of their input and only fill ceil(K/8) chunks;
+    # cs_of(K)/8 == ceil(K/8)
+    n = int(getattr(_lib.load(), query)(cs_of(K), N))
     if n < 0:
-        raise RuntimeError(f'pack_filter: unsupported channels K={K} N={N}')
-    out = torch.empty(n, dtype=torch.float32, device=w.device)
-    call('mmlf_pack_filter', ptr(w), ptr(out), cout, cin, variant, int(dgrad), _lib.stream_ptr())
-    # the kernel only fills ceil(K/8) chunks; cs_of(K)/8 == ceil(K/8)
+        raise RuntimeError(f'{who}: unsupported channels K={K} N={N}')
+    out = torch.empty(n * unit // 4, dtype=torch.float32, device=w.device)
+    call(entry, ptr(w), ptr(out), cout, cin, variant, int(dgrad), _lib.stream_ptr())
     return out
 
 
+def pack_filter(w, variant, dgrad):
+    return _pack('pack_filter', *_PACK.get(CONV_MODE, _PACK['f32']), w, variant, dgrad)
+
+
 PROFILE = None   # bench.py sets this to a list to time the 280-wide conv / weight-gradient launches with HIP events
+
+
+def _tic():
+    """PROFILE: two timing events, the first recorded on the current stream (the stream the launch goes to: the side
+    stream for the overlapped weight gradients)"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0, e1
+
+
+def _toc(events, tag, flops, nbytes):
+    events[1].record()
+    PROFILE.append((tag, flops, events[0], events[1], nbytes))
 
 
 def _amax_of(geo, t, cs):
@@ -276,53 +285,32 @@ CHECK_EXTENTS = bool(os.environ.get('MMLF_CHECK_EXTENTS'))
 EXTENT_CHECKS = 0         # launches checked so far (tests)
 
 
-def _bytes_behind(t, off_floats=0):
-    """bytes from a tensor's first element (+ an offset) to the end of its storage"""
-    return t.untyped_storage().nbytes() - t.storage_offset() * t.element_size() - 4 * off_floats
-
-
-def _check_extents(kind, ends, have):
+def _audit(entry, scalars, n_ends, kind, have):
+    """One launch against MMLF_CHECK_EXTENTS: `entry(*scalars, ends)` fills the n_ends audited ends; have maps the name of
+    a pointer argument to (its index in ends, the tensor behind it or None, the pointer's offset in floats)."""
     global EXTENT_CHECKS
-    for name, (end, t, off) in have.items():
+    ends = (ctypes.c_int64 * n_ends)()
+    call(entry, *scalars, ends)
+    for name, (k, t, off) in have.items():
         if t is None:
             continue
-        got = _bytes_behind(t, off)
-        if end > got:
-            raise RuntimeError(f'MMLF_CHECK_EXTENTS: {kind}: the launch may touch {end} bytes behind `{name}`, the tensor has {got}')
+        # bytes from the tensor's first element (+ the offset) to the end of its storage
+        got = t.untyped_storage().nbytes() - t.storage_offset() * t.element_size() - 4 * off
+        if ends[k] > got:
+            raise RuntimeError(f'MMLF_CHECK_EXTENTS: {kind}: the launch may touch {ends[k]} bytes behind `{name}`, '
+                               f'the tensor has {got}')
     EXTENT_CHECKS += 1
-
-
-def _check_conv_extents(geo, x, cs_in, K, packed, bias, N, out, cs_out, n_store, out_off, out_shift, ref, cs_ref, ax, aout,
-                        bn_partial, mask_out, mask_in):
-    import ctypes
-    e = (ctypes.c_int64 * 9)()
-    call('mmlf_audit_conv_h2', cs_in, K, N, cs_out, n_store, out_shift, cs_ref, geo.B, geo.H, geo.W, e)
-    _check_extents(f'conv {K}->{N} B={geo.B} {geo.H}x{geo.W} shift={out_shift}', e,
-                   {'in': (e[0], x, 0), 'packed': (e[1], packed, 0), 'bias': (e[2], bias, 0), 'out': (e[3], out, out_off),
-                    'ref': (e[4], ref, 0), 'in_amax': (e[5], ax, 0), 'out_amax': (e[6], aout, 0),
-                    'bn_partial': (e[7], bn_partial, 0), 'mask_out': (e[8], mask_out, 0), 'mask_in': (e[8], mask_in, 0)})
-
-
-def _check_wgrad_extents(geo, x, cs_in, cin, g, cs_g, cout, g_shift, gw, gb, workspace, ax, ag):
-    import ctypes
-    e = (ctypes.c_int64 * 7)()
-    call('mmlf_audit_wgrad_h2', cs_in, cin, cs_g, cout, g_shift, geo.B, geo.H, geo.W, e)
-    _check_extents(f'wgrad {cin}->{cout} B={geo.B} {geo.H}x{geo.W} g_shift={g_shift}', e,
-                   {'in': (e[0], x, 0), 'g': (e[1], g, 0), 'gw': (e[2], gw, 0), 'gb': (e[3], gb, 0),
-                    'workspace': (e[4], workspace, 0), 'in_amax': (e[5], ax, 0), 'g_amax': (e[6], ag, 0)})
 
 
 def relu_bwd_slice(geo, src, cs_src, c_off, ref, cs_ref, ref_off, C, dst, cs_dst):
     """dst = src[..., c_off:c_off + C] where ref[..., ref_off:ref_off + C] > 0, zero elsewhere, as a compact grid tensor"""
+    amax = getattr(dst, 'absmax', None)
     if CHECK_EXTENTS:
-        import ctypes
-        e = (ctypes.c_int64 * 4)()
-        call('mmlf_audit_relu_bwd_slice', cs_src, c_off, cs_ref, ref_off, C, cs_dst, geo.B, geo.H, geo.W, e)
-        _check_extents(f'relu_bwd_slice C={C} {cs_src}+{c_off} B={geo.B} {geo.H}x{geo.W}', e,
-                       {'src': (e[0], src, 0), 'ref': (e[1], ref, 0), 'dst': (e[2], dst, 0),
-                        'amax': (e[3], getattr(dst, 'absmax', None), 0)})
+        _audit('mmlf_audit_relu_bwd_slice', (cs_src, c_off, cs_ref, ref_off, C, cs_dst, geo.B, geo.H, geo.W), 4,
+               f'relu_bwd_slice C={C} {cs_src}+{c_off} B={geo.B} {geo.H}x{geo.W}',
+               {'src': (0, src, 0), 'ref': (1, ref, 0), 'dst': (2, dst, 0), 'amax': (3, amax, 0)})
     call('mmlf_relu_bwd_slice', ptr(src), cs_src, c_off, ptr(ref), cs_ref, ref_off, C, ptr(dst), cs_dst, geo.B, geo.H, geo.W,
-         ptr(getattr(dst, 'absmax', None)), _lib.stream_ptr())
+         ptr(amax), _lib.stream_ptr())
 
 
 THIN_MAX_N, THIN_MIN_K = 2, 64     # mmlf_conv2x2_thin: at most 2 output channels over at least 64 input channels
@@ -340,23 +328,24 @@ def wgrad(geo, x, cs_in, cin, g, cs_g, cout, g_shift, gw, gb, variant, workspace
     args = (ptr(x), cs_in, cin, ptr(g), cs_g, cout, g_shift, ptr(gw), ptr(gb), variant, 1, ptr(workspace),
             geo.B, geo.H, geo.W)
     prof = PROFILE is not None and cin >= 256 and cout >= 256
-    if prof:      # events on the stream the launch goes to (the side stream for the overlapped ones)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    if prof:
+        events = _tic()
     if CONV_MODE == 'f16x3':
         ax, ag = _amax_of(geo, x, cs_in), _amax_of(geo, g, cs_g)
         if CHECK_EXTENTS:
-            _check_wgrad_extents(geo, x, cs_in, cin, g, cs_g, cout, g_shift, gw, gb, workspace, ax, ag)
+            _audit('mmlf_audit_wgrad_h2', (cs_in, cin, cs_g, cout, g_shift, geo.B, geo.H, geo.W), 7,
+                   f'wgrad {cin}->{cout} B={geo.B} {geo.H}x{geo.W} g_shift={g_shift}',
+                   {'in': (0, x, 0), 'g': (1, g, 0), 'gw': (2, gw, 0), 'gb': (3, gb, 0), 'workspace': (4, workspace, 0),
+                    'in_amax': (5, ax, 0), 'g_amax': (6, ag, 0)})
         call('mmlf_conv2x2_wgrad_h2', *args, ptr(ax), ptr(ag), _lib.stream_ptr())
     else:
         call('mmlf_conv2x2_wgrad_split' if CONV_MODE == 'bf16x6' else 'mmlf_conv2x2_wgrad', *args, _lib.stream_ptr())
     if prof:
-        e1.record()
         # algorithmic FLOPs: the convolution's valid output positions x Cout x 4 taps x Cin, 2 FLOP per MAC (the
         # gradient of a pad-1 convolution lives at grid offset 0 with extent (H+1, W+1), of a pad-0 one at (1, 1))
         vh, vw = (geo.H + 1, geo.W + 1) if g_shift == 0 else (geo.H, geo.W)
         nbytes = 4.0 * geo.B * (cin * (geo.H * geo.W if g_shift == 0 else (geo.H + 1) * (geo.W + 1)) + cout * vh * vw)
-        PROFILE.append(('wgrad_side' if side else 'wgrad', 2.0 * geo.B * vh * vw * cout * 4 * cin, e0, e1, nbytes))
+        _toc(events, 'wgrad_side' if side else 'wgrad', 2.0 * geo.B * vh * vw * cout * 4 * cin, nbytes)
 
 
 def conv(geo, x, cs_in, K, packed, bias, N, out, cs_out, out_shift, vh, vw, relu, ref=None, cs_ref=0,
@@ -365,36 +354,38 @@ def conv(geo, x, cs_in, K, packed, bias, N, out, cs_out, out_shift, vh, vw, relu
     square per channel -- BatchNorm's training statistics without another pass over the output.
     mask_out / mask_in (f16x3 only): the ReLU mask of the output as bits (Geometry.relu_mask), written by the
     forward launch and read by the data gradient of the layer above instead of `ref`."""
+    aout = getattr(out, 'absmax', None)
     if (w_master is not None and N <= THIN_MAX_N and K >= THIN_MIN_K and cs_in <= 512 and ref is None and mask_in is None
             and mask_out is None and bn_partial is None and out_off == 0 and n_store in (None, cs_out)):
         # a matrix-vector product (the BASE / UPR head): straight from the OIHW master filter
         ws = _Workspace.get(x.device).scratch('thin_fwd', int(_lib.load().mmlf_conv2x2_thin_workspace_floats(geo.B, geo.H, geo.W)))
         call('mmlf_conv2x2_thin', ptr(x), cs_in, K, ptr(w_master), ptr(bias), N, ptr(out), cs_out, out_shift, vh, vw,
-             geo.B, geo.H, geo.W, int(relu), variant, ptr(ws), ptr(getattr(out, 'absmax', None)), _lib.stream_ptr())
+             geo.B, geo.H, geo.W, int(relu), variant, ptr(ws), ptr(aout), _lib.stream_ptr())
         return
+    n_store = cs_out if n_store is None else n_store
     # bench.py's per-launch timing: the 280-wide launches (tag 'conv') and the 70 -> 70 stream-layer launches ('conv70')
     prof = PROFILE is not None and ((K >= 256 and N >= 256) or (K == N and 64 <= K < 128))
     if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    args = (ptr(x), cs_in, K, ptr(packed), ptr(bias), N, ptr(out) + 4 * out_off, cs_out,
-            cs_out if n_store is None else n_store, out_shift, vh, vw, geo.B, geo.H, geo.W, int(relu), ptr(ref), cs_ref)
+        events = _tic()
+    args = (ptr(x), cs_in, K, ptr(packed), ptr(bias), N, ptr(out) + 4 * out_off, cs_out, n_store, out_shift, vh, vw,
+            geo.B, geo.H, geo.W, int(relu), ptr(ref), cs_ref)
     if CONV_MODE == 'f16x3':
         ax = _amax_of(geo, x, cs_in)
         if CHECK_EXTENTS:
-            _check_conv_extents(geo, x, cs_in, K, packed, bias, N, out, cs_out, cs_out if n_store is None else n_store, out_off,
-                                out_shift, ref, cs_ref, ax, getattr(out, 'absmax', None), bn_partial, mask_out, mask_in)
-        call('mmlf_conv2x2_h2', *args, ptr(ax), ptr(getattr(out, 'absmax', None)), ptr(bn_partial), ptr(mask_out),
-             ptr(mask_in), _lib.stream_ptr())
+            _audit('mmlf_audit_conv_h2', (cs_in, K, N, cs_out, n_store, out_shift, cs_ref, geo.B, geo.H, geo.W), 9,
+                   f'conv {K}->{N} B={geo.B} {geo.H}x{geo.W} shift={out_shift}',
+                   {'in': (0, x, 0), 'packed': (1, packed, 0), 'bias': (2, bias, 0), 'out': (3, out, out_off),
+                    'ref': (4, ref, 0), 'in_amax': (5, ax, 0), 'out_amax': (6, aout, 0), 'bn_partial': (7, bn_partial, 0),
+                    'mask_out': (8, mask_out, 0), 'mask_in': (8, mask_in, 0)})
+        call('mmlf_conv2x2_h2', *args, ptr(ax), ptr(aout), ptr(bn_partial), ptr(mask_out), ptr(mask_in), _lib.stream_ptr())
     else:
         call('mmlf_conv2x2_split' if CONV_MODE == 'bf16x6' else 'mmlf_conv2x2', *args, _lib.stream_ptr())
     if prof:
-        e1.record()
         # algorithmic FLOPs of this launch: valid output positions x N x 4 taps x K, 2 FLOP per MAC; algorithmic BYTES: the
         # input's and the output's stored extents once each (a pad-1 convolution reads (H, W) and writes (H+1, W+1), a pad-0
         # one the other way round), float32, unpadded channels
         nbytes = 4.0 * geo.B * (K * (geo.H * geo.W if out_shift == 0 else (geo.H + 1) * (geo.W + 1)) + N * vh * vw)
-        PROFILE.append(('conv' if K >= 256 else 'conv70', 2.0 * geo.B * vh * vw * N * 4 * K, e0, e1, nbytes))
+        _toc(events, 'conv' if K >= 256 else 'conv70', 2.0 * geo.B * vh * vw * N * 4 * K, nbytes)
 
 
 # ---------------------------------------------------------------------------------------------- 3x3 filters (--model_ksize 3)
@@ -402,47 +393,32 @@ def conv(geo, x, cs_in, K, packed, bias, N, out, cs_out, out_shift, vh, vw, relu
 # convolutions, input and output at grid offset (1, 1) with extent (H, W).
 
 def pack_filter3(w, variant, dgrad):
-    cout, cin = w.shape[0], w.shape[1]
-    K, N = (cout, cin) if dgrad else (cin, cout)
-    n = int(_lib.load().mmlf_packed_filter3x3_floats(cs_of(K), N))
-    if n < 0:
-        raise RuntimeError(f'pack_filter3: unsupported channels K={K} N={N}')
-    out = torch.empty(n, dtype=torch.float32, device=w.device)
-    call('mmlf_pack_filter3x3', ptr(w), ptr(out), cout, cin, variant, int(dgrad), _lib.stream_ptr())
-    return out
+    return _pack('pack_filter3', *_PACK3, w, variant, dgrad)
 
 
 def conv3(geo, x, cs_in, K, packed, bias, N, out, cs_out, relu, ref=None, cs_ref=0, n_store=None, out_off=0):
     """3x3 forward (or, on a dgrad-packed filter, data gradient): out[q + P + 1] from x[q + dy*P + dx]"""
     n_store = cs_out if n_store is None else n_store
     if CHECK_EXTENTS:
-        import ctypes
-        e = (ctypes.c_int64 * 5)()
-        call('mmlf_audit_conv3x3', cs_in, K, N, cs_out, n_store, cs_ref if ref is not None else 0, geo.B, geo.H, geo.W, e)
-        _check_extents(f'conv3x3 {K}->{N} B={geo.B} {geo.H}x{geo.W}', e,
-                       {'in': (e[0], x, 0), 'packed': (e[1], packed, 0), 'bias': (e[2], bias, 0), 'out': (e[3], out, out_off),
-                        'ref': (e[4], ref, 0)})
+        _audit('mmlf_audit_conv3x3', (cs_in, K, N, cs_out, n_store, cs_ref if ref is not None else 0, geo.B, geo.H, geo.W), 5,
+               f'conv3x3 {K}->{N} B={geo.B} {geo.H}x{geo.W}',
+               {'in': (0, x, 0), 'packed': (1, packed, 0), 'bias': (2, bias, 0), 'out': (3, out, out_off), 'ref': (4, ref, 0)})
     prof = PROFILE is not None and K >= 256 and N >= 256
     if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+        events = _tic()
     call('mmlf_conv3x3', ptr(x), cs_in, K, ptr(packed), ptr(bias), N, ptr(out) + 4 * out_off, cs_out, n_store,
          geo.B, geo.H, geo.W, int(relu), ptr(ref), cs_ref, _lib.stream_ptr())
     if prof:
-        e1.record()
         nbytes = 4.0 * geo.B * geo.H * geo.W * (K + N)
-        PROFILE.append(('conv3x3', 2.0 * geo.B * geo.H * geo.W * N * 9 * K, e0, e1, nbytes))
+        _toc(events, 'conv3x3', 2.0 * geo.B * geo.H * geo.W * N * 9 * K, nbytes)
 
 
 def wgrad3(geo, x, cs_in, cin, g, cs_g, cout, gw, gb, variant, workspace):
     """3x3 weight + bias gradient, accumulated into gw / gb"""
     if CHECK_EXTENTS:
-        import ctypes
-        e = (ctypes.c_int64 * 5)()
-        call('mmlf_audit_wgrad3x3', cs_in, cin, cs_g, cout, geo.B, geo.H, geo.W, e)
-        _check_extents(f'wgrad3x3 {cin}->{cout} B={geo.B} {geo.H}x{geo.W}', e,
-                       {'in': (e[0], x, 0), 'g': (e[1], g, 0), 'gw': (e[2], gw, 0), 'gb': (e[3], gb, 0),
-                        'workspace': (e[4], workspace, 0)})
+        _audit('mmlf_audit_wgrad3x3', (cs_in, cin, cs_g, cout, geo.B, geo.H, geo.W), 5,
+               f'wgrad3x3 {cin}->{cout} B={geo.B} {geo.H}x{geo.W}',
+               {'in': (0, x, 0), 'g': (1, g, 0), 'gw': (2, gw, 0), 'gb': (3, gb, 0), 'workspace': (4, workspace, 0)})
     call('mmlf_conv3x3_wgrad', ptr(x), cs_in, cin, ptr(g), cs_g, cout, ptr(gw), ptr(gb), variant, 1, ptr(workspace),
          geo.B, geo.H, geo.W, _lib.stream_ptr())
 
@@ -455,11 +431,25 @@ class BlockSpec:
         self.prefix, self.cin, self.cout, self.bn = prefix, cin, cout, bn
 
 
+class _Rec:
+    """What a block's forward leaves on the tape for its backward.  x / cs_x: the block's input; x_relu: x is the output of a
+    block without BatchNorm (whose trailing ReLU the data gradient of conv1 applies), xmask: the bits of that ReLU if it left
+    any; y: conv1's output behind its ReLU, ymask: that ReLU as bits (f16 split); z: conv2's output where BatchNorm or
+    nothing follows; scale ... sinv: BatchNorm's coefficients and saved statistics; eval: they are the RUNNING statistics."""
+    __slots__ = ('spec', 'var', 'x', 'cs_x', 'x_relu', 'xmask', 'y', 'ymask', 'z', 'scale', 'shift', 'smean', 'sinv', 'eval')
+
+    def __init__(self, spec, var, x, cs_x, x_relu, xmask, y, ymask, z):
+        self.spec, self.var, self.x, self.cs_x, self.x_relu, self.xmask = spec, var, x, cs_x, x_relu, xmask
+        self.y, self.ymask, self.z = y, ymask, z
+        self.scale = self.shift = self.smean = self.sinv = None
+        self.eval = False
+
+
 class Trunk:
     """Native forward/backward of in_net_hv / in_net_id / out_net (non-cross) with 2x2 or 3x3 filters, and, with 2x2
     filters, with or without BatchNorm (batchnorm=False: model_no_batchnorm, reference feed_forward.py:122-137 -- both ReLUs
     of a block ride in the convolutions' epilogues, training and inference take the same launches, and the gradient behind a
-    block's trailing ReLU comes out of the data gradient of the convolution above it: _block_fwd_relu, _block_bwd).
+    block's trailing ReLU comes out of the data gradient of the convolution above it: _block_fwd, _block_bwd).
     `params` maps state_dict keys to device tensors.
     ksize 3 runs the exact-f32 3x3 kernels (conv3 / wgrad3): filters packed per layer, BatchNorm statistics by
     mmlf_bn_stats_train, the data gradient's ReLU by `ref`, inference with BatchNorm folded into conv2."""
@@ -514,77 +504,111 @@ class Trunk:
             block(spec, VAR_IDENTITY, False)
         return _Workspace.get(dev).packed_filters(items)
 
+    def _pack(self, w, var, dgrad):
+        return (pack_filter3 if self.ksize == 3 else pack_filter)(w, var, dgrad)
+
+    def _packed(self, packs, p, name, var, dgrad):
+        """the packed form of filter `name`: from the step's prepack, or else packed now"""
+        pk = packs.get((name, var, dgrad))
+        return pk if pk is not None else self._pack(p[name], var, dgrad)
+
+    # ------------------------------------------------------------------ the two convolutions of a block, by kernel size
+    # 2x2: conv1 (pad 1) takes extent (H, W) at grid offset (1, 1) to (H+1, W+1) at offset 0, conv2 (pad 0) takes it back; a
+    # data gradient goes the way of the other convolution's forward.  3x3: "same" convolutions, one geometry for all.
+    def _conv(self, geo, second, x, cs_in, K, packed, bias, N, out, cs_out, relu, ref=None, cs_ref=0, n_store=None, out_off=0,
+              **only2x2):
+        """forward of a block's first / second convolution.  only2x2: bn_partial, mask_out, mask_in, w_master, variant of
+        `conv`, for what the 3x3 kernels do not have (the callers' capability conditions leave them None there)"""
+        if self.ksize == 3:
+            assert all(v is None for v in only2x2.values()), only2x2
+            conv3(geo, x, cs_in, K, packed, bias, N, out, cs_out, relu, ref=ref, cs_ref=cs_ref, n_store=n_store, out_off=out_off)
+            return
+        out_shift, vh, vw = (geo.P + 1, geo.H, geo.W) if second else (0, geo.H + 1, geo.W + 1)
+        conv(geo, x, cs_in, K, packed, bias, N, out, cs_out, out_shift, vh, vw, relu, ref=ref, cs_ref=cs_ref, n_store=n_store,
+             out_off=out_off, **only2x2)
+
+    def _dgrad(self, geo, second, g, cs_g, K, packed, N, dx, cs_dx, **relu_of):
+        """data gradient of a block's first / second convolution (packed: its dgrad form); relu_of: `ref`, `cs_ref` or
+        `mask_in` of a ReLU in front of that convolution, applied in the epilogue"""
+        self._conv(geo, not second, g, cs_g, K, packed, None, N, dx, cs_dx, False, **relu_of)
+
+    def _wgrad(self, geo, second, x, cs_in, cin, g, cs_g, cout, gw, gb, var, side=False):
+        """weight + bias gradient of a block's first / second convolution, accumulated into gw / gb"""
+        ws = _Workspace.get(x.device).wgrad_ws(geo, cin, cout, side=side)
+        if self.ksize == 3:
+            wgrad3(geo, x, cs_in, cin, g, cs_g, cout, gw, gb, var, ws)
+        else:
+            wgrad(geo, x, cs_in, cin, g, cs_g, cout, geo.P + 1 if second else 0, gw, gb, var, ws, side=side)
+
     # ------------------------------------------------------------------ forward
-    def _block_fwd(self, geo, spec, var, x, cs_x, p, train, rec_list, out=None, cs_out=None, c_off=0, packs=None,
+    def _block_fwd(self, geo, spec, var, x, cs_x, x_relu, xmask, p, train, rec_list, out=None, cs_out=None, c_off=0, packs=None,
                    tracked=None, deferred=None):
-        """x: grid tensor (extent H,W at (1,1)).  Returns the block output grid tensor.
+        """One block: conv1 (pad 1) -> ReLU -> conv2 (pad 0), then BatchNorm -> ReLU (bn True), ReLU (bn False) or nothing (the
+        head).  conv1's ReLU always rides in its epilogue; conv2's does where conv2 is the block's last operation.
+        x: grid tensor (extent H,W at (1,1)); x_relu: x is the output of a block without BatchNorm, xmask: the bits of that
+        ReLU if it left any (both kept for backward).  rec_list: where to leave what backward needs, None = nothing is saved.
+        out (a stream's last block): the block output goes to the channel slice [c_off, c_off + cout) of the concat buffer.
         deferred (a list): the BatchNorm-apply + ReLU pass into `out` is NOT launched; (z, scale, shift) is appended
-        and the caller applies all four streams' last blocks in one pass over the concat buffer (Trunk.forward)."""
+        and the caller applies all four streams' last blocks in one pass over the concat buffer (Trunk.forward).
+        Returns (output grid tensor, its channel stride, the bits of its ReLU mask or None)."""
         dev = x.device
         ws = _Workspace.get(dev)
-        B, H, W, P = geo.B, geo.H, geo.W, geo.P
-        cmid, cs_mid = spec.cout, cs_of(spec.cout)
-        w1, b1 = p[f'{spec.prefix}.0.weight'], p[f'{spec.prefix}.0.bias']
-        w2, b2 = p[f'{spec.prefix}.2.weight'], p[f'{spec.prefix}.2.bias']
+        B, H, W = geo.B, geo.H, geo.W
+        C, cs_mid = spec.cout, cs_of(spec.cout)
+        pre = spec.prefix
+        w1, b1, w2, b2 = p[f'{pre}.0.weight'], p[f'{pre}.0.bias'], p[f'{pre}.2.weight'], p[f'{pre}.2.bias']
         packs = packs or {}
-        k3 = self.ksize == 3
-        pack = pack_filter3 if k3 else pack_filter
-        thin = cmid <= THIN_MAX_N and spec.cin >= THIN_MIN_K and not k3   # the head: matrix-vector kernels, y is tiny
-        pk1 = packs.get((f'{spec.prefix}.0.weight', var, False))
-        if pk1 is None and not thin:
-            pk1 = pack(w1, var, False)
-        folded = spec.bn and not train and rec_list is None        # inference: BatchNorm folded into conv2
-        new_out = spec.bn and out is None                          # the block output is a buffer of its own
-        got = geo.bufs([cs_mid] * ((1 if folded else 2) + (1 if new_out else 0)), dev)   # one zeroing launch for all
+        save = rec_list is not None
+        f16 = CONV_MODE == 'f16x3' and self.ksize == 2             # ReLU bits and fused statistics: the f16-split kernels'
+        thin = C <= THIN_MAX_N and spec.cin >= THIN_MIN_K and self.ksize == 2     # the head: matrix-vector kernels, y is tiny
+        bits = save and f16 and not thin
+        folded = spec.bn is True and not train and not save       # inference: BatchNorm folded into conv2
+        relu2 = spec.bn is False or folded                         # conv2 is the block's last operation: it writes the output
+        fused_stats = spec.bn is True and train and f16            # BatchNorm's statistics from conv2's epilogue
+        new_out = spec.bn is not None and out is None              # the block output is a buffer of its own
+        pk1 = None if thin else self._packed(packs, p, f'{pre}.0.weight', var, False)
+        if spec.bn is False:      # (these blocks pack conv2's filter ahead of conv1's launch)
+            pk2 = self._packed(packs, p, f'{pre}.2.weight', var, False)
+        got = geo.bufs([cs_mid] * ((1 if relu2 else 2) + (1 if new_out else 0)), dev)   # one zeroing launch for all
         y = got[0]
-        z = None if folded else got[1]
+        z = None if relu2 else got[1]
         if new_out:
             out, cs_out, c_off = got[-1], cs_mid, 0
-        ymask = geo.relu_mask(dev) if (rec_list is not None and CONV_MODE == 'f16x3' and not thin and not k3) else None
-        if k3:
-            conv3(geo, x, cs_x, spec.cin, pk1, b1, cmid, y, cs_mid, True)
-        else:
-            conv(geo, x, cs_x, spec.cin, pk1, b1, cmid, y, cs_mid, 0, H + 1, W + 1, True, mask_out=ymask, w_master=w1,
-                 variant=var)
-        if spec.bn and not train and rec_list is None:   # rec_list is None when nothing is saved for backward
-            # inference: BatchNorm(eval) is a per-channel affine map -> fold it into conv2 and fuse the ReLU
-            C = spec.cout
+        ymask = geo.relu_mask(dev) if bits else None
+        # the mask of the block's output is read by the data gradient of the NEXT block's first convolution (_block_bwd):
+        # a slice of the concat buffer has no such consumer (mmlf_relu_bwd_slice reads the activations)
+        omask = geo.relu_mask(dev) if bits and relu2 and new_out else None
+        head = {'w_master': w1, 'variant': var} if thin else {}    # (straight from the master filter)
+        self._conv(geo, False, x, cs_x, spec.cin, pk1, b1, C, y, cs_mid, True, mask_out=ymask, **head)
+        if folded:
+            # BatchNorm(eval) is a per-channel affine map -> fold it into conv2 and fuse the ReLU
             coef = torch.empty(2 * C, dtype=torch.float32, device=dev)
-            call('mmlf_bn_coeffs_eval', ptr(p[f'{spec.prefix}.3.weight']), ptr(p[f'{spec.prefix}.3.bias']),
-                 ptr(p[f'{spec.prefix}.3.running_mean']), ptr(p[f'{spec.prefix}.3.running_var']), self.eps,
-                 ptr(coef), ptr(coef[C:]), C, _lib.stream_ptr())
+            call('mmlf_bn_coeffs_eval', ptr(p[f'{pre}.3.weight']), ptr(p[f'{pre}.3.bias']), ptr(p[f'{pre}.3.running_mean']),
+                 ptr(p[f'{pre}.3.running_var']), self.eps, ptr(coef), ptr(coef[C:]), C, _lib.stream_ptr())
             w2f, b2f = torch.empty_like(w2), torch.empty_like(b2)
-            call('mmlf_fold_bn_eval3x3' if k3 else 'mmlf_fold_bn_eval', ptr(w2), ptr(b2), ptr(coef), ptr(coef[C:]), ptr(w2f),
-                 ptr(b2f), C, C, _lib.stream_ptr())
-            pk2 = pack(w2f, var, False)
-            n_store = cs_out if new_out else C
-            if k3:
-                conv3(geo, y, cs_mid, cmid, pk2, b2f, cmid, out, cs_out, True, n_store=n_store, out_off=c_off)
-            else:
-                conv(geo, y, cs_mid, cmid, pk2, b2f, cmid, out, cs_out, P + 1, H, W, True, n_store=n_store, out_off=c_off)
-            return out, cs_out
-        pk2 = packs.get((f'{spec.prefix}.2.weight', var, False))
-        if pk2 is None:
-            pk2 = pack(w2, var, False)
-        fused_stats = spec.bn and train and CONV_MODE == 'f16x3' and not k3      # statistics from the conv epilogue
-        if k3:
-            conv3(geo, y, cs_mid, cmid, pk2, b2, cmid, z, cs_mid, False)
-        else:
-            conv(geo, y, cs_mid, cmid, pk2, b2, cmid, z, cs_mid, P + 1, H, W, False,
-                 bn_partial=ws.partial if fused_stats else None)
-        rec = {'spec': spec, 'var': var, 'x': x, 'cs_x': cs_x, 'y': y, 'z': z, 'ymask': ymask}
-        if not spec.bn:
-            if rec_list is not None:
-                rec_list.append(rec)
-            return z, cs_mid
-        C = spec.cout
+            call('mmlf_fold_bn_eval3x3' if self.ksize == 3 else 'mmlf_fold_bn_eval', ptr(w2), ptr(b2), ptr(coef), ptr(coef[C:]),
+                 ptr(w2f), ptr(b2f), C, C, _lib.stream_ptr())
+            pk2, b2 = self._pack(w2f, var, False), b2f
+        elif spec.bn is not False:
+            pk2 = self._packed(packs, p, f'{pre}.2.weight', var, False)
+        rec = None
+        if save:
+            rec = _Rec(spec, var, x, cs_x, x_relu, xmask, y, ymask, z)
+            rec_list.append(rec)
+        if relu2:
+            self._conv(geo, True, y, cs_mid, C, pk2, b2, C, out, cs_out, True, n_store=cs_out if new_out else C, out_off=c_off,
+                       mask_out=omask)
+            return out, cs_out, omask
+        self._conv(geo, True, y, cs_mid, C, pk2, b2, C, z, cs_mid, False, bn_partial=ws.partial if fused_stats else None)
+        if spec.bn is None:
+            return z, cs_mid, None
         coef = torch.empty(4 * C, dtype=torch.float32, device=dev)
         scale, shift, smean, sinv = coef[:C], coef[C:2 * C], coef[2 * C:3 * C], coef[3 * C:]
-        g, bt = p[f'{spec.prefix}.3.weight'], p[f'{spec.prefix}.3.bias']
-        rm, rv = p[f'{spec.prefix}.3.running_mean'], p[f'{spec.prefix}.3.running_var']
+        g, bt = p[f'{pre}.3.weight'], p[f'{pre}.3.bias']
+        rm, rv = p[f'{pre}.3.running_mean'], p[f'{pre}.3.running_var']
         if train:
             if fused_stats:
-                nblk = int(_lib.load().mmlf_conv2x2_blocks(cmid, cmid, B, H, W))
+                nblk = int(_lib.load().mmlf_conv2x2_blocks(C, C, B, H, W))
                 call('mmlf_bn_stats_finalize', ptr(ws.partial), nblk, C, ptr(g), ptr(bt), ptr(rm), ptr(rv),
                      self.momentum, self.eps, ptr(smean), ptr(sinv), ptr(scale), ptr(shift), B, H, W,
                      _lib.stream_ptr())
@@ -593,64 +617,26 @@ class Trunk:
                      self.eps, ptr(smean), ptr(sinv), ptr(scale), ptr(shift), ptr(ws.partial), BN_BLOCKS, B, H, W,
                      _lib.stream_ptr())
             if tracked is None:
-                p[f'{spec.prefix}.3.num_batches_tracked'].add_(1)
+                p[f'{pre}.3.num_batches_tracked'].add_(1)
             else:
-                tracked.append(p[f'{spec.prefix}.3.num_batches_tracked'])
+                tracked.append(p[f'{pre}.3.num_batches_tracked'])
         else:
             call('mmlf_bn_coeffs_eval', ptr(g), ptr(bt), ptr(rm), ptr(rv), self.eps, ptr(scale), ptr(shift), C,
                  _lib.stream_ptr())
-            if rec_list is not None:
+            if save:
                 # eval-mode BatchNorm under autograd (reference train/cli.py:227-230, --train_eval_mode): the
                 # statistics are constants, so backward is dz = g * gamma * invstd with the RUNNING statistics
                 smean.copy_(rm)
                 sinv.copy_(torch.rsqrt(rv.double() + self.eps).float())
-                rec['eval'] = True
-        c_store = cs_out if new_out else C
+                rec.eval = True
         if deferred is not None:
             deferred.append((z, scale, shift))
         else:
-            call('mmlf_bn_apply_relu', ptr(z), cs_mid, C, ptr(scale), ptr(shift), ptr(out), cs_out, c_off, c_store,
-                 B, H, W, ptr(out.absmax), _lib.stream_ptr())
-        rec.update(scale=scale, shift=shift, smean=smean, sinv=sinv)
-        if rec_list is not None:
-            rec_list.append(rec)
-        return out, cs_out
-
-    def _block_fwd_relu(self, geo, spec, var, x, cs_x, x_relu, xmask, p, rec_list, out=None, cs_out=None, c_off=0, packs=None):
-        """A block without BatchNorm: conv(pad 1) -> ReLU -> conv(pad 0) -> ReLU, both ReLUs in the convolutions' epilogues.
-        out (a stream's last block): the second convolution writes the channel slice [c_off, c_off + cout) of the concat
-        buffer.  x_relu: x is the output of such a block, xmask: the bits of that ReLU if it left any (kept for backward).
-        Returns (output grid tensor, its channel stride, the bits of its ReLU mask or None)."""
-        dev = x.device
-        H, W, P = geo.H, geo.W, geo.P
-        C, cs_mid = spec.cout, cs_of(spec.cout)
-        w1, b1 = p[f'{spec.prefix}.0.weight'], p[f'{spec.prefix}.0.bias']
-        w2, b2 = p[f'{spec.prefix}.2.weight'], p[f'{spec.prefix}.2.bias']
-        packs = packs or {}
-        # (never the matrix-vector kernels: cout is chs >= 2 with cin = 3 views or chs, or 4 chs >= 8; the head is _block_fwd's)
-        pk1 = packs.get((f'{spec.prefix}.0.weight', var, False))
-        if pk1 is None:
-            pk1 = pack_filter(w1, var, False)
-        pk2 = packs.get((f'{spec.prefix}.2.weight', var, False))
-        if pk2 is None:
-            pk2 = pack_filter(w2, var, False)
-        new_out = out is None
-        got = geo.bufs([cs_mid] * (2 if new_out else 1), dev)
-        y = got[0]
-        if new_out:
-            out, cs_out, c_off = got[1], cs_mid, 0
-        bits = rec_list is not None and CONV_MODE == 'f16x3'
-        ymask = geo.relu_mask(dev) if bits else None
-        # the mask of the block's output is read by the data gradient of the NEXT block's first convolution (_block_bwd):
-        # a slice of the concat buffer has no such consumer (mmlf_relu_bwd_slice reads the activations)
-        omask = geo.relu_mask(dev) if bits and new_out else None
-        conv(geo, x, cs_x, spec.cin, pk1, b1, C, y, cs_mid, 0, H + 1, W + 1, True, mask_out=ymask)
-        conv(geo, y, cs_mid, C, pk2, b2, C, out, cs_out, P + 1, H, W, True, n_store=cs_out if new_out else C, out_off=c_off,
-             mask_out=omask)
-        if rec_list is not None:
-            rec_list.append({'spec': spec, 'var': var, 'x': x, 'cs_x': cs_x, 'y': y, 'z': None, 'ymask': ymask,
-                             'x_relu': x_relu, 'xmask': xmask})
-        return out, cs_out, omask
+            call('mmlf_bn_apply_relu', ptr(z), cs_mid, C, ptr(scale), ptr(shift), ptr(out), cs_out, c_off,
+                 cs_out if new_out else C, B, H, W, ptr(out.absmax), _lib.stream_ptr())
+        if save:
+            rec.scale, rec.shift, rec.smean, rec.sinv = scale, shift, smean, sinv
+        return out, cs_out, None
 
     def forward(self, p, stacks, train, save, packed=None):
         """stacks: four (B, views, 3, H, W) contiguous float32 device tensors.
@@ -687,44 +673,27 @@ class Trunk:
                 call('mmlf_pack_nchw', ptr(stacks[s]), cin0, ptr(x), cs_of(cin0), B, H, W, ptr(x.absmax), _lib.stream_ptr())
             cs_x = cs_of(cin0)
             recs = []
-            xmask = None
+            x_relu, xmask = False, None
             for k, spec in enumerate(blocks):
                 last = k == len(blocks) - 1
-                if spec.bn is False:
-                    x, cs_x, xmask = self._block_fwd_relu(geo, spec, var, x, cs_x, k > 0, xmask, p, recs if save else None,
-                                                          out=concat if last else None, cs_out=4 * self.chs,
-                                                          c_off=s * self.chs, packs=packs)
-                    continue
-                x, cs_x = self._block_fwd(geo, spec, var, x, cs_x, p, train, recs if save else None,
-                                          out=concat if last else None, cs_out=4 * self.chs, c_off=s * self.chs, packs=packs,
-                                          tracked=tracked, deferred=deferred if last else None)
+                x, cs_x, xmask = self._block_fwd(geo, spec, var, x, cs_x, x_relu, xmask, p, train, recs if save else None,
+                                                 out=concat if last else None, cs_out=4 * self.chs, c_off=s * self.chs,
+                                                 packs=packs, tracked=tracked, deferred=deferred if last else None)
+                x_relu = spec.bn is False
             tape['streams'].append(recs)
-            if not save:
-                del recs[:]
         if deferred:
-            import ctypes
             arr = lambda k: (ctypes.c_void_p * 4)(*[ptr(d[k]) for d in deferred])
             call('mmlf_bn_apply_relu4', arr(0), cs_of(self.chs), self.chs, arr(1), arr(2), ptr(concat), 4 * self.chs,
                  B, H, W, ptr(concat.absmax), _lib.stream_ptr())
             del deferred[:]
         if save and not self.batchnorm:
             tape['concat'] = concat
-        x, cs_x = concat, 4 * self.chs
-        xmask = None
-        for k, spec in enumerate(self.out_blocks):
-            if spec.bn is False:
-                # (k == 0: x is the concat buffer, whose ReLU mmlf_relu_bwd_slice applies per stream in backward)
-                x, cs_x, xmask = self._block_fwd_relu(geo, spec, VAR_IDENTITY, x, cs_x, k > 0, xmask, p,
-                                                      tape['out'] if save else None, packs=packs)
-                continue
-            x_in = x
-            x, cs_x = self._block_fwd(geo, spec, VAR_IDENTITY, x, cs_x, p, train, tape['out'] if save else None, packs=packs,
-                                      tracked=tracked)
-            if save and not self.batchnorm and k > 0:      # the head behind a block without BatchNorm
-                assert tape['out'][-1]['x'] is x_in
-                tape['out'][-1].update(x_relu=True, xmask=xmask)
-            if not save:
-                del tape['out'][:]
+        # (x_relu False: x is the concat buffer, whose ReLU mmlf_relu_bwd_slice applies per stream in backward)
+        x, cs_x, x_relu, xmask = concat, 4 * self.chs, False, None
+        for spec in self.out_blocks:
+            x, cs_x, xmask = self._block_fwd(geo, spec, VAR_IDENTITY, x, cs_x, x_relu, xmask, p, train,
+                                             tape['out'] if save else None, packs=packs, tracked=tracked)
+            x_relu = spec.bn is False
         if tracked:
             # the shared stream nets' counters appear twice: two forwards per pass, as in the reference
             # (feed_forward.py:222-235 calls in_net_hv for h and v) -- one entry per tensor with its count, since a
@@ -739,35 +708,34 @@ class Trunk:
 
     # ------------------------------------------------------------------ backward
     def _block_bwd(self, geo, rec, p, grads, gy, cs_gy, c_off, need_dx, after_bn=None, overlap=False, packs=None):
-        """gy: gradient w.r.t. the block output (grid, extent (H,W)).  Returns dX grid tensor.
+        """gy: gradient w.r.t. the block output (grid, extent (H,W)).  Returns (dX grid tensor or None, event, keep).
         after_bn: called once this block's BatchNorm-backward kernels are enqueued.  overlap: run the
         first convolution's weight gradient on the side stream AFTER the data gradient is enqueued, so that
         it (matrix-core bound) runs beside the BatchNorm-backward kernels of the block underneath (HBM
-        bound), which only need the data gradient; returns (dX, event, tensors to keep alive until the event) then."""
-        spec, var = rec['spec'], rec['var']
+        bound), which only need the data gradient; event: that launch's end, keep: the tensors to keep alive until
+        the event (both None without overlap)."""
+        spec, var = rec.spec, rec.var
         dev = gy.device
         ws = _Workspace.get(dev)
-        B, H, W, P = geo.B, geo.H, geo.W, geo.P
+        B, H, W = geo.B, geo.H, geo.W
         C, cs_mid = spec.cout, cs_of(spec.cout)
-        x, cs_x, y, z = rec['x'], rec['cs_x'], rec['y'], rec['z']
+        x, cs_x, y, z = rec.x, rec.cs_x, rec.y, rec.z
         pre = spec.prefix
         sp = _lib.stream_ptr
         packs = packs or {}
-        k3 = self.ksize == 3
+        f16 = CONV_MODE == 'f16x3' and self.ksize == 2
+        gw1, gb1, gw2, gb2 = (grads[f'{pre}.{k}'] for k in ('0.weight', '0.bias', '2.weight', '2.bias'))
 
-        def packed(name, w):
-            pk = packs.get((name, var, True))
-            return pk if pk is not None else (pack_filter3 if k3 else pack_filter)(w, var, True)
-
+        # the ReLU of y in conv2's data gradient: by the bits conv1's forward launch left, or else by y itself
+        y_relu = {'mask_in': rec.ymask} if rec.ymask is not None and f16 else {'ref': y, 'cs_ref': cs_mid}
         # x is the output of a block without BatchNorm: the data gradient of conv1 applies that block's trailing ReLU, so what
         # comes out is already the gradient behind it (dz of the block underneath) and costs no pass of its own.  In the f16
         # split the mask comes as the bits the producing conv2 launch left: that launch and this one have the same (B, H, W),
         # the same N (the block's width), out_shift P + 1 and a buffer of channel stride cs_x of their own, so they run the same
         # kernel and epilogue orientation and agree on the private word layout.  Otherwise x itself is the reference.
         x_relu = {}
-        if rec.get('x_relu'):
-            x_relu = ({'mask_in': rec['xmask']} if rec.get('xmask') is not None and CONV_MODE == 'f16x3'
-                      else {'ref': x, 'cs_ref': cs_x})
+        if rec.x_relu:
+            x_relu = {'mask_in': rec.xmask} if rec.xmask is not None and f16 else {'ref': x, 'cs_ref': cs_x}
 
         # this block's gradient buffers, one zeroing launch: dz (behind BatchNorm), dy, dx
         got = geo.bufs(([cs_mid] if spec.bn else []) + [cs_mid] + ([cs_x] if need_dx else []), dev)
@@ -775,61 +743,41 @@ class Trunk:
         dx = got[-1] if need_dx else None
         if spec.bn:
             coef = torch.empty(3 * C, dtype=torch.float32, device=dev)
-            call('mmlf_bn_bwd_reduce', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec['scale']), ptr(rec['shift']),
-                 ptr(p[f'{pre}.3.weight']), ptr(rec['smean']), ptr(rec['sinv']), ptr(grads[f'{pre}.3.weight']),
+            call('mmlf_bn_bwd_reduce', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
+                 ptr(p[f'{pre}.3.weight']), ptr(rec.smean), ptr(rec.sinv), ptr(grads[f'{pre}.3.weight']),
                  ptr(grads[f'{pre}.3.bias']), 1, ptr(coef), ptr(ws.partial), BN_BLOCKS, B, H, W, sp())
-            if rec.get('eval'):
+            if rec.eval:
                 coef[C:].zero_()            # no batch-statistics terms: dz = k1 * g (dgamma / dbeta sums are the same)
             dz = got[0]
-            call('mmlf_bn_bwd_apply', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec['scale']), ptr(rec['shift']),
-                 ptr(rec['smean']), ptr(coef), ptr(dz), cs_mid, B, H, W, ptr(dz.absmax), sp())
+            call('mmlf_bn_bwd_apply', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
+                 ptr(rec.smean), ptr(coef), ptr(dz), cs_mid, B, H, W, ptr(dz.absmax), sp())
         else:
             assert c_off == 0 and cs_gy == cs_mid
             dz = gy
         if after_bn:
             after_bn()
-        w1, w2 = p[f'{pre}.0.weight'], p[f'{pre}.2.weight']
-        if k3:
-            # conv2: weight / bias gradient, data gradient fused with the ReLU of y; conv1: the same without the ReLU
-            wgrad3(geo, y, cs_mid, C, dz, cs_mid, C, grads[f'{pre}.2.weight'], grads[f'{pre}.2.bias'], var, ws.wgrad_ws(geo, C, C))
-            conv3(geo, dz, cs_mid, C, packed(f'{pre}.2.weight', w2), None, C, dy, cs_mid, False, ref=y, cs_ref=cs_mid)
-            del dz, got
-            wgrad3(geo, x, cs_x, spec.cin, dy, cs_mid, C, grads[f'{pre}.0.weight'], grads[f'{pre}.0.bias'], var,
-                   ws.wgrad_ws(geo, spec.cin, C))
-            if not need_dx:
-                return None
-            conv3(geo, dy, cs_mid, C, packed(f'{pre}.0.weight', w1), None, spec.cin, dx, cs_x, False)
-            return dx
-        # conv2 (pad 0): weight/bias gradient, then data gradient fused with the ReLU mask of y
-        wgrad(geo, y, cs_mid, C, dz, cs_mid, C, P + 1, grads[f'{pre}.2.weight'], grads[f'{pre}.2.bias'], var,
-              ws.wgrad_ws(geo, C, C))
-        pk = packed(f'{pre}.2.weight', w2)
-        if rec.get('ymask') is not None and CONV_MODE == 'f16x3':
-            conv(geo, dz, cs_mid, C, pk, None, C, dy, cs_mid, 0, H + 1, W + 1, False, mask_in=rec['ymask'])
-        else:
-            conv(geo, dz, cs_mid, C, pk, None, C, dy, cs_mid, 0, H + 1, W + 1, False, ref=y, cs_ref=cs_mid)
+        # conv2: weight / bias gradient, then data gradient fused with the ReLU of y
+        self._wgrad(geo, True, y, cs_mid, C, dz, cs_mid, C, gw2, gb2, var)
+        self._dgrad(geo, True, dz, cs_mid, C, self._packed(packs, p, f'{pre}.2.weight', var, True), C, dy, cs_mid, **y_relu)
         del dz, got
-        # conv1 (pad 1)
+        # conv1: the same, with the ReLU (if any) of the block underneath
         if overlap and need_dx:
-            pk = packed(f'{pre}.0.weight', w1)
-            conv(geo, dy, cs_mid, C, pk, None, spec.cin, dx, cs_x, P + 1, H, W, False, **x_relu)
+            self._dgrad(geo, False, dy, cs_mid, C, self._packed(packs, p, f'{pre}.0.weight', var, True), spec.cin, dx, cs_x,
+                        **x_relu)
             main = torch.cuda.current_stream()
             ready = main.record_event()
             with torch.cuda.stream(ws.side):
                 ws.side.wait_event(ready)
-                wgrad(geo, x, cs_x, spec.cin, dy, cs_mid, C, 0, grads[f'{pre}.0.weight'], grads[f'{pre}.0.bias'],
-                      var, ws.wgrad_ws(geo, spec.cin, C, side=True), side=True)
+                self._wgrad(geo, False, x, cs_x, spec.cin, dy, cs_mid, C, gw1, gb1, var, side=True)
                 done = ws.side.record_event()
             # x and dy are read by the side stream: the caller keeps them alive until the main stream has waited
             # for `done` (no record_stream: deferred reuse makes the caching allocator grow and stall)
             return dx, done, (x, dy)
-        wgrad(geo, x, cs_x, spec.cin, dy, cs_mid, C, 0, grads[f'{pre}.0.weight'], grads[f'{pre}.0.bias'], var,
-              ws.wgrad_ws(geo, spec.cin, C))
-        if not need_dx:
-            return None
-        pk = packed(f'{pre}.0.weight', w1)
-        conv(geo, dy, cs_mid, C, pk, None, spec.cin, dx, cs_x, P + 1, H, W, False, **x_relu)
-        return dx
+        self._wgrad(geo, False, x, cs_x, spec.cin, dy, cs_mid, C, gw1, gb1, var)
+        if need_dx:
+            self._dgrad(geo, False, dy, cs_mid, C, self._packed(packs, p, f'{pre}.0.weight', var, True), spec.cin, dx, cs_x,
+                        **x_relu)
+        return dx, None, None
 
     def backward(self, p, tape, grad_output, grads, on_done=None):
         """grad_output: (B,oc,H,W) NCHW.  grads: dict name -> tensor, ACCUMULATED into
@@ -858,17 +806,15 @@ class Trunk:
 
         while recs:
             rec = recs.pop()
-            wide = OVERLAP_WGRAD and rec['spec'].cin >= 128 and self.ksize == 2
-            res = self._block_bwd(geo, rec, p, grads, g, cs_g, 0, True, after_bn=settle, overlap=wide, packs=tape.get('packs'))
+            wide = OVERLAP_WGRAD and rec.spec.cin >= 128 and self.ksize == 2
+            g, event, keep = self._block_bwd(geo, rec, p, grads, g, cs_g, 0, True, after_bn=settle, overlap=wide,
+                                             packs=tape['packs'])
             settle()                        # (blocks without BatchNorm never called it)
-            if wide:
-                g, ev, keep = res
-                pending = (ev, rec['spec'].prefix, keep)
-            else:
-                g = res
-                if on_done:
-                    on_done(rec['spec'].prefix)
-            cs_g = rec['cs_x']
+            if event is not None:
+                pending = (event, rec.spec.prefix, keep)
+            elif on_done:
+                on_done(rec.spec.prefix)
+            cs_g = rec.cs_x
         # g is now the gradient w.r.t. the concat buffer (cs = 4*chs); streams read channel slices
         for s in reversed(range(4)):
             recs = tape['streams'][s]
@@ -882,7 +828,7 @@ class Trunk:
                 relu_bwd_slice(geo, g, cs_g, s * self.chs, tape['concat'], cs_g, s * self.chs, self.chs, gs, cs_s)
             while recs:
                 rec = recs.pop()
-                gs = self._block_bwd(geo, rec, p, grads, gs, cs_s, off, need_dx=bool(recs), packs=tape.get('packs'))
-                cs_s, off = rec['cs_x'], 0
+                gs, _, _ = self._block_bwd(geo, rec, p, grads, gs, cs_s, off, need_dx=bool(recs), packs=tape['packs'])
+                cs_s, off = rec.cs_x, 0
             if on_done and s in (2, 0):      # shared stream nets: complete after the I (resp. H) stream
                 on_done('in_net_id' if s == 2 else 'in_net_hv')

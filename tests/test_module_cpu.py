@@ -101,13 +101,94 @@ def test_model_unet_fallback_matches_reference_golden(dev):
     np.testing.assert_allclose(out['logvar'].cpu().numpy(), g['eval_logvar'], **tol)
 
 
+_MINI_HEADER = '''
+/* a block comment that names a call: mmlf_x(int a, float *b);
+ * and spans lines */
+#ifndef MINI_H
+#define MINI_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define MINI_VERSION 3
+enum { MINI_A = 0, MINI_B = 1 };
+typedef struct mini_desc {
+    const float *w;   /* a member */
+    int32_t n, m;
+} mini_desc;
+const char *mini_error(void);
+int mini_version(void);
+int64_t mini_size(int K, int32_t N);   // a line comment: mmlf_y(
+int mini_launch(const float *in, int cs /* stride */, const mini_desc *table, uint32_t *mask, float scale,
+                double eps, int64_t n, long long hw, void *stream);
+int mini_arrays(const float *const z[4], const int cs[4], float *const amax[4], int B);
+#ifdef __cplusplus
+}
+#endif
+#endif
+'''
+
+
+def test_signatures_from_header_on_a_small_header():
+    """one prototype of every declarator form the binding maps, beside a struct typedef, an enum, macros and comments"""
+    from mmlf_amd._lib import signatures_from_header
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    assert signatures_from_header(_MINI_HEADER) == {
+        'mini_error': (ctypes.c_char_p, []),
+        'mini_version': (i, []),
+        'mini_size': (ctypes.c_int64, [i, ctypes.c_int32]),
+        'mini_launch': (i, [vp, i, vp, vp, ctypes.c_float, ctypes.c_double, ctypes.c_int64, ctypes.c_longlong, vp]),
+        'mini_arrays': (i, [vp, vp, vp, i]),
+    }
+
+
+@pytest.mark.parametrize('proto', [
+    'int f(unsigned n);',                   # a type word the table does not hold
+    'int f(size_t n);',
+    'short f(void);',                       # ... as a return type
+    'float *f(void);',                      # a pointer result that is no `const char *`
+    'int f(int (*cb)(int), void *stream);',  # a function pointer
+    'int f(int);',                          # an unnamed parameter
+    'int f(int a, ...);',
+    'int f(int a) { return a; }',           # a definition
+    'struct s { int a; };',                 # a struct outside a typedef
+    'int f(int a); int f(int a);',          # the same name twice
+])
+def test_signatures_from_header_refuses_what_it_does_not_recognise(proto):
+    from mmlf_amd._lib import signatures_from_header
+    with pytest.raises(ValueError) as e:
+        signatures_from_header('int ok(int a);\n' + proto)
+    assert proto.split(';')[0].split('{')[0].strip()[:8] in str(e.value)      # the message names the prototype
+
+
+def test_signatures_of_the_real_header_pinned():
+    """three entry points written out, so that a parser regression cannot pass as 'the header says so'"""
+    from mmlf_amd import _lib
+    vp, i, i64, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
+    assert len(_lib.SIGNATURES) == 73
+    assert _lib.SIGNATURES['mmlf_conv2x2_h2'] == (i, [vp, i, i, vp, vp, i, vp, i, i, i, i, i, i, i, i, i, vp, i,
+                                                      vp, vp, vp, vp, vp, vp])
+    assert len(_lib.SIGNATURES['mmlf_conv2x2_h2'][1]) == 24
+    assert _lib.SIGNATURES['mmlf_adam_step'] == (i, [vp, vp, vp, vp, i64, d, d, d, d, i64, d, vp])
+    assert _lib.SIGNATURES['mmlf_bn_apply_relu4'] == (i, [vp, i, i, vp, vp, vp, i, i, i, i, vp, vp])
+    assert _lib.SIGNATURES['mmlf_last_error'] == (ctypes.c_char_p, [])
+    assert _lib.SIGNATURES['mmlf_lmm_to_discrete'][1][7] is ctypes.c_longlong
+
+
 def test_c_abi_exports_every_declared_symbol():
+    import subprocess
     from mmlf_amd import _lib
     from mmlf_amd.csrc import build
     build.build(verbose=False)
     header = open(os.path.join(ROOT, 'include', 'mmlf_hip.h')).read()
-    declared = set(re.findall(r'\b(mmlf_[a-z0-9_]+)\s*\(', header))
-    assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    declared = set(_lib.SIGNATURES)
+    # every entry point the header's text names (comments included) is one the parser found
+    assert set(re.findall(r'\b(mmlf_[a-z0-9_]+)\s*\(', header)) <= declared
+    # the library defines exactly the declared entry points: none missing, none undeclared (mmlf_debug_oob_counts exists
+    # under -DMMLF_BOUNDS_DEBUG only, which is not the product build)
+    nm = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.split() and line.split()[-1].startswith('mmlf_')}
+    assert exported == declared, exported ^ declared
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name

@@ -1,0 +1,161 @@
+"""What the host code of the trunk (mmlf_amd/engine.py) does, as one JSON file: for a set of tiny configurations, every
+call through the C ABI with its arguments, the `on_done` keys of Trunk.backward in call order, sha256 of the output, of
+every gradient and of every buffer, and the allocator's peak.  Two trees whose files are equal issue the same launches
+with the same arguments and compute the same bits: the oracle of a refactor of the host code.
+
+    python tools/launch_trace.py OUT.json          (in each tree; then compare the files, or `--diff A.json B.json`)
+
+Uses only FeedForward, mmlf_amd.synth and engine.call (which it wraps), so it runs unchanged in older trees.
+"""
+import ctypes
+import hashlib
+import itertools
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mmlf_amd import _lib, engine, synth                    # noqa: E402
+from mmlf_amd.feed_forward import FeedForward               # noqa: E402
+
+DEV = 'cuda:0'
+B, H, W = 2, 7, 5
+KW = dict(model_in_blocks=2, model_out_blocks=3, model_views=3, model_cross=False, model_unet=False,
+          model_batchnorm_momentum=0.1, val_disp_min=-3.5, val_disp_max=3.5)
+HEADS = {1: {}, 2: {'model_uncert': True}, 36: {'model_discrete': True}}          # BASE, UPR, DPP (4 x 3 views x 3)
+NETS = {'k2bn': dict(model_ksize=2, model_no_batchnorm=False), 'k2nobn': dict(model_ksize=2, model_no_batchnorm=True),
+        'k3bn': dict(model_ksize=3, model_no_batchnorm=False)}
+PASSES = {'train_saved': (True, True), 'eval_folded': (False, False), 'eval_saved': (False, True),
+          'train_nograd': (True, False)}                                             # name: (train, save)
+
+TRACE = []
+_real_call = engine.call
+
+
+def _arg(a, ctype):
+    if isinstance(a, ctypes.Array):
+        return ['a', [(('p' if v else 0) if a._type_ is ctypes.c_void_p else v) for v in a]]
+    if ctype is ctypes.c_void_p:
+        return 'p' if a else 0
+    if a is None:
+        return 0
+    assert isinstance(a, (int, float)), (a, ctype)
+    return a
+
+
+def _traced_call(name, *args):
+    types = _lib.SIGNATURES[name][1]
+    assert len(types) == len(args), name
+    TRACE.append([name, [_arg(a, t) for a, t in zip(args, types)]])
+    _real_call(name, *args)
+
+
+engine.call = _traced_call            # (engine binds `call` by name at import)
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def model_of(net, chs, oc):
+    kw = dict(KW, model_chs=chs, model_uncert=False, model_discrete=False, **NETS[net])
+    kw.update(HEADS[oc])
+    model = FeedForward(**kw)
+    state = synth.formula_state([(k, v.shape) for k, v in model.state_dict().items()], seed=5)
+    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in state.items()})
+    assert model._native_ok and model.out_chs == oc
+    return model.to(DEV)
+
+
+def run(net, chs, oc, pas, mode='f16x3', overlap=True, packed=False, extents=False):
+    train, save = PASSES[pas]
+    engine.CONV_MODE, engine.OVERLAP_WGRAD, engine.CHECK_EXTENTS = mode, overlap, extents
+    engine.EXTENT_CHECKS = 0
+    model = model_of(net, chs, oc)
+    dev = torch.device(DEV)
+    stacks = [torch.from_numpy(s).to(dev) for s in synth.synth_inputs(B, H, views=3, seed=3, ps_w=W)[0]]
+    gout = torch.from_numpy(np.random.RandomState(17).uniform(-1, 1, (B, oc, H, W)).astype(np.float32)).to(dev)
+    p = {n: t.detach() for n, t in model._tensor_dict().items()}
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    del TRACE[:]
+    done = []
+    with torch.no_grad():
+        if packed:        # inputs already in the grid layout, as the Ensamble hands them over
+            geo = engine.Geometry(B, H, W, model._trunk.ksize)
+            cs = engine.cs_of(9)
+            xs = geo.bufs([cs] * 4, dev)
+            for t, x in zip(stacks, xs):
+                engine.call('mmlf_pack_nchw', t.data_ptr(), 9, x.data_ptr(), cs, B, H, W, x.absmax.data_ptr(),
+                            _lib.stream_ptr())
+            out, tape = model._trunk.forward(p, None, train, save, packed=(geo, xs))
+        else:
+            out, tape = model._trunk.forward(p, stacks, train, save)
+        grads = {}
+        if save:
+            grads = {n: torch.zeros_like(p[n]) for n in model._param_names}
+            model._trunk.backward(p, tape, gout, grads, on_done=done.append)
+    torch.cuda.synchronize()
+    res = {'trace': [list(t) for t in TRACE], 'on_done': done, 'peak_bytes': torch.cuda.max_memory_allocated(),
+           'sha256': dict({'out': sha(out)}, **{f'grad/{n}': sha(g) for n, g in grads.items()},
+                          **{f'buffer/{n}': sha(t) for n, t in model.named_buffers()})}
+    if extents:
+        res['extent_checks'] = engine.EXTENT_CHECKS
+    return res
+
+
+def configurations():
+    for net, chs, oc, pas in itertools.product(NETS, (6, 32), HEADS, PASSES):
+        for mode in (('f16x3', 'bf16x6', 'f32') if net != 'k3bn' else ('f16x3',)):
+            # the side-stream weight gradient exists for wide 2x2 blocks in backward only
+            for overlap in ((True, False) if chs == 32 and net != 'k3bn' and PASSES[pas][1] else (True,)):
+                yield f'{net} chs={chs} oc={oc} {pas} {mode} overlap={int(overlap)}', (net, chs, oc, pas, mode, overlap)
+    yield 'packed: k2bn chs=6 oc=2 eval_folded', ('k2bn', 6, 2, 'eval_folded', 'f16x3', True, True)
+    for net, pas in (('k2bn', 'train_saved'), ('k2nobn', 'train_saved'), ('k3bn', 'train_saved'), ('k2bn', 'eval_folded')):
+        yield f'extents: {net} chs=32 oc=2 {pas}', (net, 32, 2, pas, 'f16x3', True, False, True)
+
+
+def diff(a, b):
+    """prints what differs between two result files; exit status 1 if anything does"""
+    ra, rb = json.load(open(a)), json.load(open(b))
+    bad = 0
+    for key in sorted(set(ra) | set(rb)):
+        x, y = ra.get(key), rb.get(key)
+        if x is None or y is None:
+            print(f'{key}: only in {a if y is None else b}')
+            bad += 1
+            continue
+        for field in sorted(set(x) | set(y)):
+            if x.get(field) == y.get(field):
+                continue
+            bad += 1
+            if field == 'trace':
+                k = next((i for i, (u, v) in enumerate(zip(x[field], y[field])) if u != v), min(len(x[field]), len(y[field])))
+                print(f'{key}: trace differs at call {k} of {len(x[field])} / {len(y[field])}:')
+                print('   ', x[field][k] if k < len(x[field]) else None)
+                print('   ', y[field][k] if k < len(y[field]) else None)
+            elif field == 'sha256':
+                print(f'{key}: tensors differ:', [n for n in x[field] if x[field][n] != y[field].get(n)])
+            else:
+                print(f'{key}: {field}: {x.get(field)} != {y.get(field)}')
+    print(f'{len(ra)} / {len(rb)} configurations, {bad} differences')
+    return 1 if bad else 0
+
+
+def main():
+    if sys.argv[1] == '--diff':
+        sys.exit(diff(sys.argv[2], sys.argv[3]))
+    results = {}
+    for key, args in configurations():
+        results[key] = run(*args)
+    os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
+    with open(sys.argv[1], 'w') as f:
+        json.dump(results, f, indent=0, sort_keys=True)
+    print(f'{len(results)} configurations, {sum(len(r["trace"]) for r in results.values())} calls -> {sys.argv[1]}')
+
+
+if __name__ == '__main__':
+    main()
