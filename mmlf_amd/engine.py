@@ -435,14 +435,18 @@ class _Rec:
     """What a block's forward leaves on the tape for its backward.  x / cs_x: the block's input; x_relu: x is the output of a
     block without BatchNorm (whose trailing ReLU the data gradient of conv1 applies), xmask: the bits of that ReLU if it left
     any; y: conv1's output behind its ReLU, ymask: that ReLU as bits (f16 split); z: conv2's output where BatchNorm or
-    nothing follows; scale ... sinv: BatchNorm's coefficients and saved statistics; eval: they are the RUNNING statistics."""
-    __slots__ = ('spec', 'var', 'x', 'cs_x', 'x_relu', 'xmask', 'y', 'ymask', 'z', 'scale', 'shift', 'smean', 'sinv', 'eval')
+    nothing follows; scale ... sinv: BatchNorm's coefficients and saved statistics; eval: they are the RUNNING statistics.
+    bn: backward goes through BatchNorm (spec.bn, unless the forward folded it into conv2: a frozen evaluation, whose block is
+    then a ReLU-only one with the filter whose data-gradient form is pk2d)."""
+    __slots__ = ('spec', 'var', 'x', 'cs_x', 'x_relu', 'xmask', 'y', 'ymask', 'z', 'scale', 'shift', 'smean', 'sinv', 'eval',
+                 'bn', 'pk2d')
 
     def __init__(self, spec, var, x, cs_x, x_relu, xmask, y, ymask, z):
         self.spec, self.var, self.x, self.cs_x, self.x_relu, self.xmask = spec, var, x, cs_x, x_relu, xmask
         self.y, self.ymask, self.z = y, ymask, z
         self.scale = self.shift = self.smean = self.sinv = None
         self.eval = False
+        self.bn, self.pk2d = spec.bn, None
 
 
 class Trunk:
@@ -477,9 +481,11 @@ class Trunk:
             raise ValueError('native trunk needs an even model_chs with 4*model_chs a multiple of 8')
 
     # ------------------------------------------------------------------ filters
-    def _prepack(self, p, dev, with_dgrad):
+    def _prepack(self, p, dev, with_dgrad, input_grads=None, fold=False):
         """every packed filter a step needs -- forward and, with_dgrad, data-gradient forms -- from ONE launch (f16 split
-        only; the other modes pack per layer).  Keys: (parameter name, variant, dgrad)."""
+        only; the other modes pack per layer).  input_grads: per stream, whether backward will form the gradient of the
+        stream's input (the data-gradient form of its first filter).  fold: BatchNorm is folded into conv2 (_block_fwd packs
+        the folded filter itself), so conv2's master filter is not packed.  Keys: (parameter name, variant, dgrad)."""
         if CONV_MODE != 'f16x3' or dev.type != 'cuda' or self.ksize != 2:
             return {}
         items = []
@@ -487,21 +493,24 @@ class Trunk:
         def add(name, var, dgrad):
             items.append(((name, var, dgrad), p[name], var, dgrad))
 
-        def block(spec, var, first):
+        def block(spec, var, need_dx):
             thin = spec.cout <= THIN_MAX_N and spec.cin >= THIN_MIN_K      # the head's first conv runs from the master filter
+            own2 = not (fold and spec.bn is True)
             if not thin:
                 add(f'{spec.prefix}.0.weight', var, False)
-            add(f'{spec.prefix}.2.weight', var, False)
+            if own2:
+                add(f'{spec.prefix}.2.weight', var, False)
             if with_dgrad:
-                add(f'{spec.prefix}.2.weight', var, True)
-                if not first:
+                if own2:
+                    add(f'{spec.prefix}.2.weight', var, True)
+                if need_dx:
                     add(f'{spec.prefix}.0.weight', var, True)
 
-        for _, var, blocks in self.streams:
+        for s, (_, var, blocks) in enumerate(self.streams):
             for k, spec in enumerate(blocks):
-                block(spec, var, k == 0)
+                block(spec, var, k > 0 or bool(input_grads and input_grads[s]))
         for spec in self.out_blocks:
-            block(spec, VAR_IDENTITY, False)
+            block(spec, VAR_IDENTITY, True)
         return _Workspace.get(dev).packed_filters(items)
 
     def _pack(self, w, var, dgrad):
@@ -542,7 +551,7 @@ class Trunk:
 
     # ------------------------------------------------------------------ forward
     def _block_fwd(self, geo, spec, var, x, cs_x, x_relu, xmask, p, train, rec_list, out=None, cs_out=None, c_off=0, packs=None,
-                   tracked=None, deferred=None):
+                   tracked=None, deferred=None, fold=False):
         """One block: conv1 (pad 1) -> ReLU -> conv2 (pad 0), then BatchNorm -> ReLU (bn True), ReLU (bn False) or nothing (the
         head).  conv1's ReLU always rides in its epilogue; conv2's does where conv2 is the block's last operation.
         x: grid tensor (extent H,W at (1,1)); x_relu: x is the output of a block without BatchNorm, xmask: the bits of that
@@ -550,6 +559,7 @@ class Trunk:
         out (a stream's last block): the block output goes to the channel slice [c_off, c_off + cout) of the concat buffer.
         deferred (a list): the BatchNorm-apply + ReLU pass into `out` is NOT launched; (z, scale, shift) is appended
         and the caller applies all four streams' last blocks in one pass over the concat buffer (Trunk.forward).
+        fold: eval-mode BatchNorm is folded into conv2 (inference, and the saving forward of a frozen net: Trunk.forward).
         Returns (output grid tensor, its channel stride, the bits of its ReLU mask or None)."""
         dev = x.device
         ws = _Workspace.get(dev)
@@ -562,7 +572,7 @@ class Trunk:
         f16 = CONV_MODE == 'f16x3' and self.ksize == 2             # ReLU bits and fused statistics: the f16-split kernels'
         thin = C <= THIN_MAX_N and spec.cin >= THIN_MIN_K and self.ksize == 2     # the head: matrix-vector kernels, y is tiny
         bits = save and f16 and not thin
-        folded = spec.bn is True and not train and not save       # inference: BatchNorm folded into conv2
+        folded = spec.bn is True and fold                          # BatchNorm folded into conv2
         relu2 = spec.bn is False or folded                         # conv2 is the block's last operation: it writes the output
         fused_stats = spec.bn is True and train and f16            # BatchNorm's statistics from conv2's epilogue
         new_out = spec.bn is not None and out is None              # the block output is a buffer of its own
@@ -595,6 +605,9 @@ class Trunk:
         if save:
             rec = _Rec(spec, var, x, cs_x, x_relu, xmask, y, ymask, z)
             rec_list.append(rec)
+            if folded:
+                # backward is the ReLU-only block's, through the FOLDED filter (the weights are frozen: no gradient of theirs)
+                rec.bn, rec.pk2d = False, self._pack(w2f, var, True)
         if relu2:
             self._conv(geo, True, y, cs_mid, C, pk2, b2, C, out, cs_out, True, n_store=cs_out if new_out else C, out_off=c_off,
                        mask_out=omask)
@@ -638,11 +651,16 @@ class Trunk:
             rec.scale, rec.shift, rec.smean, rec.sinv = scale, shift, smean, sinv
         return out, cs_out, None
 
-    def forward(self, p, stacks, train, save, packed=None):
+    def forward(self, p, stacks, train, save, packed=None, input_grads=None, frozen=False):
         """stacks: four (B, views, 3, H, W) contiguous float32 device tensors.
         packed (instead of stacks): (Geometry, [four grid tensors of channel stride cs_of(3 views), with their amax arrays]) --
         inputs some other kernel already wrote in the grid layout (the Ensamble's mmlf_shift_pack).
-        Returns (output NCHW (B,oc,H,W), ctx or None)."""
+        input_grads (with save): four bools, the streams whose input gradient backward will be asked for -- their first
+        filters' data-gradient forms join the step's one packing launch (backward packs them itself otherwise).
+        frozen (with save): backward will be called with grads=None (no parameter wants a gradient).  In eval mode a 2x2 trunk
+        with BatchNorm then runs the inference launches (BatchNorm folded into conv2) and keeps what a model_no_batchnorm
+        forward keeps: the same output bits as without a tape, and a backward without any BatchNorm launch.
+        Returns (output NCHW (B,oc,H,W), tape or None)."""
         if packed is not None:
             geo, xs_in = packed
             B, H, W = geo.B, geo.H, geo.W
@@ -655,7 +673,11 @@ class Trunk:
             geo = Geometry(B, H, W, self.ksize)
             cin0 = n * c
         _Workspace.get(dev).enter_stream()
-        packs = self._prepack(p, dev, save)
+        # BatchNorm folded into conv2: inference, and the frozen evaluation that is differentiated in its inputs (3x3 trunks
+        # have no ReLU-only backward and keep the unfolded form under a tape)
+        fold = self.batchnorm and not train and (not save or (bool(frozen) and self.ksize == 2))
+        relu_only = not self.batchnorm or fold                  # every block below the head ends in conv2's own ReLU
+        packs = self._prepack(p, dev, save, input_grads, fold)
         tracked = []                  # BatchNorm counters of this pass: ONE increment launch at its end
         tape = {'geo': geo, 'streams': [], 'out': [], 'packs': packs}
         if packed is not None:
@@ -665,7 +687,6 @@ class Trunk:
             xs.append(geo.buf(cs_of(cin0), dev))
         # the four streams' last BatchNorm-apply passes write quarter rows of the concat buffer: one pass for all four
         # (whole rows) when they are real passes (not folded into conv2) and the channel count allows it
-        fold = not train and not save
         deferred = [] if (not fold and self.chs % 2 == 0 and all(b[-1].bn for _, _, b in self.streams)) else None
         for s, (key, var, blocks) in enumerate(self.streams):
             x = xs[s]
@@ -678,22 +699,22 @@ class Trunk:
                 last = k == len(blocks) - 1
                 x, cs_x, xmask = self._block_fwd(geo, spec, var, x, cs_x, x_relu, xmask, p, train, recs if save else None,
                                                  out=concat if last else None, cs_out=4 * self.chs, c_off=s * self.chs,
-                                                 packs=packs, tracked=tracked, deferred=deferred if last else None)
-                x_relu = spec.bn is False
+                                                 packs=packs, tracked=tracked, deferred=deferred if last else None, fold=fold)
+                x_relu = relu_only
             tape['streams'].append(recs)
         if deferred:
             arr = lambda k: (ctypes.c_void_p * 4)(*[ptr(d[k]) for d in deferred])
             call('mmlf_bn_apply_relu4', arr(0), cs_of(self.chs), self.chs, arr(1), arr(2), ptr(concat), 4 * self.chs,
                  B, H, W, ptr(concat.absmax), _lib.stream_ptr())
             del deferred[:]
-        if save and not self.batchnorm:
+        if save and relu_only:
             tape['concat'] = concat
         # (x_relu False: x is the concat buffer, whose ReLU mmlf_relu_bwd_slice applies per stream in backward)
         x, cs_x, x_relu, xmask = concat, 4 * self.chs, False, None
         for spec in self.out_blocks:
             x, cs_x, xmask = self._block_fwd(geo, spec, VAR_IDENTITY, x, cs_x, x_relu, xmask, p, train,
-                                             tape['out'] if save else None, packs=packs, tracked=tracked)
-            x_relu = spec.bn is False
+                                             tape['out'] if save else None, packs=packs, tracked=tracked, fold=fold)
+            x_relu = relu_only
         if tracked:
             # the shared stream nets' counters appear twice: two forwards per pass, as in the reference
             # (feed_forward.py:222-235 calls in_net_hv for h and v) -- one entry per tensor with its count, since a
@@ -709,6 +730,8 @@ class Trunk:
     # ------------------------------------------------------------------ backward
     def _block_bwd(self, geo, rec, p, grads, gy, cs_gy, c_off, need_dx, after_bn=None, overlap=False, packs=None):
         """gy: gradient w.r.t. the block output (grid, extent (H,W)).  Returns (dX grid tensor or None, event, keep).
+        grads None: no parameter gradient is wanted -- no weight-gradient launch, no side stream, and BatchNorm's pass 1 only
+        where its coefficients need the batch sums (train-mode statistics).
         after_bn: called once this block's BatchNorm-backward kernels are enqueued.  overlap: run the
         first convolution's weight gradient on the side stream AFTER the data gradient is enqueued, so that
         it (matrix-core bound) runs beside the BatchNorm-backward kernels of the block underneath (HBM
@@ -724,7 +747,10 @@ class Trunk:
         sp = _lib.stream_ptr
         packs = packs or {}
         f16 = CONV_MODE == 'f16x3' and self.ksize == 2
-        gw1, gb1, gw2, gb2 = (grads[f'{pre}.{k}'] for k in ('0.weight', '0.bias', '2.weight', '2.bias'))
+        bn = rec.bn                      # (False where a frozen evaluation folded BatchNorm into conv2: ReLU-only backward)
+        assert grads is None or rec.pk2d is None, 'a frozen forward (BatchNorm folded) has no parameter gradients'
+        if grads is not None:
+            gw1, gb1, gw2, gb2 = (grads[f'{pre}.{k}'] for k in ('0.weight', '0.bias', '2.weight', '2.bias'))
 
         # the ReLU of y in conv2's data gradient: by the bits conv1's forward launch left, or else by y itself
         y_relu = {'mask_in': rec.ymask} if rec.ymask is not None and f16 else {'ref': y, 'cs_ref': cs_mid}
@@ -738,16 +764,26 @@ class Trunk:
             x_relu = {'mask_in': rec.xmask} if rec.xmask is not None and f16 else {'ref': x, 'cs_ref': cs_x}
 
         # this block's gradient buffers, one zeroing launch: dz (behind BatchNorm), dy, dx
-        got = geo.bufs(([cs_mid] if spec.bn else []) + [cs_mid] + ([cs_x] if need_dx else []), dev)
-        dy = got[1 if spec.bn else 0]
+        got = geo.bufs(([cs_mid] if bn else []) + [cs_mid] + ([cs_x] if need_dx else []), dev)
+        dy = got[1 if bn else 0]
         dx = got[-1] if need_dx else None
-        if spec.bn:
-            coef = torch.empty(3 * C, dtype=torch.float32, device=dev)
-            call('mmlf_bn_bwd_reduce', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
-                 ptr(p[f'{pre}.3.weight']), ptr(rec.smean), ptr(rec.sinv), ptr(grads[f'{pre}.3.weight']),
-                 ptr(grads[f'{pre}.3.bias']), 1, ptr(coef), ptr(ws.partial), BN_BLOCKS, B, H, W, sp())
-            if rec.eval:
-                coef[C:].zero_()            # no batch-statistics terms: dz = k1 * g (dgamma / dbeta sums are the same)
+        if bn:
+            if grads is None and rec.eval:
+                # running statistics and nobody reads dgamma / dbeta: dz = k1 * g with k1 = gamma * invstd, the saved scale
+                coef = torch.zeros(3 * C, dtype=torch.float32, device=dev)
+                coef[:C].copy_(rec.scale)
+            else:
+                coef = torch.empty(3 * C, dtype=torch.float32, device=dev)
+                if grads is None:       # the batch sums feed the coefficients; their dgamma / dbeta form goes to scratch
+                    dgb = ws.scratch('bn_dgamma_dbeta', 2 * C)
+                    dgamma, dbeta, acc = dgb[:C], dgb[C:2 * C], 0
+                else:
+                    dgamma, dbeta, acc = grads[f'{pre}.3.weight'], grads[f'{pre}.3.bias'], 1
+                call('mmlf_bn_bwd_reduce', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
+                     ptr(p[f'{pre}.3.weight']), ptr(rec.smean), ptr(rec.sinv), ptr(dgamma), ptr(dbeta), acc, ptr(coef),
+                     ptr(ws.partial), BN_BLOCKS, B, H, W, sp())
+                if rec.eval:
+                    coef[C:].zero_()        # no batch-statistics terms: dz = k1 * g (dgamma / dbeta sums are the same)
             dz = got[0]
             call('mmlf_bn_bwd_apply', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
                  ptr(rec.smean), ptr(coef), ptr(dz), cs_mid, B, H, W, ptr(dz.absmax), sp())
@@ -757,11 +793,13 @@ class Trunk:
         if after_bn:
             after_bn()
         # conv2: weight / bias gradient, then data gradient fused with the ReLU of y
-        self._wgrad(geo, True, y, cs_mid, C, dz, cs_mid, C, gw2, gb2, var)
-        self._dgrad(geo, True, dz, cs_mid, C, self._packed(packs, p, f'{pre}.2.weight', var, True), C, dy, cs_mid, **y_relu)
+        if grads is not None:
+            self._wgrad(geo, True, y, cs_mid, C, dz, cs_mid, C, gw2, gb2, var)
+        pk2d = rec.pk2d if rec.pk2d is not None else self._packed(packs, p, f'{pre}.2.weight', var, True)
+        self._dgrad(geo, True, dz, cs_mid, C, pk2d, C, dy, cs_mid, **y_relu)
         del dz, got
         # conv1: the same, with the ReLU (if any) of the block underneath
-        if overlap and need_dx:
+        if overlap and need_dx and grads is not None:
             self._dgrad(geo, False, dy, cs_mid, C, self._packed(packs, p, f'{pre}.0.weight', var, True), spec.cin, dx, cs_x,
                         **x_relu)
             main = torch.cuda.current_stream()
@@ -773,16 +811,21 @@ class Trunk:
             # x and dy are read by the side stream: the caller keeps them alive until the main stream has waited
             # for `done` (no record_stream: deferred reuse makes the caching allocator grow and stall)
             return dx, done, (x, dy)
-        self._wgrad(geo, False, x, cs_x, spec.cin, dy, cs_mid, C, gw1, gb1, var)
+        if grads is not None:
+            self._wgrad(geo, False, x, cs_x, spec.cin, dy, cs_mid, C, gw1, gb1, var)
         if need_dx:
             self._dgrad(geo, False, dy, cs_mid, C, self._packed(packs, p, f'{pre}.0.weight', var, True), spec.cin, dx, cs_x,
                         **x_relu)
         return dx, None, None
 
-    def backward(self, p, tape, grad_output, grads, on_done=None):
+    def backward(self, p, tape, grad_output, grads, on_done=None, input_grads=None):
         """grad_output: (B,oc,H,W) NCHW.  grads: dict name -> tensor, ACCUMULATED into
-        (the caller zeroes them).  on_done(key) is called when every gradient of 'out_net.k' /
-        'in_net_id' / 'in_net_hv' has been enqueued (gradient-bucket all-reduce hook)."""
+        (the caller zeroes them), or None: no parameter gradient is formed (no weight-gradient launch at all; required
+        for a tape of forward(frozen=True)).  on_done(key) is called when every gradient of 'out_net.k' /
+        'in_net_id' / 'in_net_hv' has been enqueued (gradient-bucket all-reduce hook).
+        input_grads: four bools (streams H, V, I, D), the view stacks whose gradient is wanted; default none.  Returns a list
+        of four entries: the (B, views, 3, H, W) float32 gradient of a wanted stack, None for the others.  The parameter
+        gradients do not depend on it: the same weight-gradient launches in the same order."""
         geo = tape['geo']
         dev = grad_output.device
         _Workspace.get(dev).enter_stream()
@@ -792,6 +835,9 @@ class Trunk:
         call('mmlf_pack_nchw', ptr(grad_output.contiguous()), self.oc, ptr(g), cs, B, H, W, ptr(g.absmax),
              _lib.stream_ptr())
         cs_g = cs
+        want = [bool(w) for w in input_grads] if input_grads is not None else [False] * 4
+        assert len(want) == 4
+        dstacks = [None] * 4
         recs = tape['out']
         main = torch.cuda.current_stream()
         pending = None                      # (event, prefix, tensors) of a weight gradient still running on the side stream
@@ -821,14 +867,20 @@ class Trunk:
             if s == 2:
                 settle()                    # out_net.0's weight gradient ran beside the first stream's BatchNorm kernels
             gs, cs_s, off = g, cs_g, s * self.chs
-            if not self.batchnorm:
+            if 'concat' in tape:
                 # the stream's last ReLU wrote its slice of the concat buffer: the gradient behind it, as a compact tensor
                 cs_s, off = cs_of(self.chs), 0
                 gs = geo.buf(cs_s, dev)
                 relu_bwd_slice(geo, g, cs_g, s * self.chs, tape['concat'], cs_g, s * self.chs, self.chs, gs, cs_s)
             while recs:
                 rec = recs.pop()
-                gs, _, _ = self._block_bwd(geo, rec, p, grads, gs, cs_s, off, need_dx=bool(recs), packs=tape['packs'])
+                gs, _, _ = self._block_bwd(geo, rec, p, grads, gs, cs_s, off, need_dx=bool(recs) or want[s],
+                                           packs=tape['packs'])
                 cs_s, off = rec.cs_x, 0
+            if want[s]:
+                # gs: the gradient of the stream's packed input, extent (H, W) at (1, 1), 3 views channels of cs_s
+                dstacks[s] = torch.empty((B, self.views, 3, H, W), dtype=torch.float32, device=dev)
+                call('mmlf_unpack_nchw', ptr(gs), cs_s, ptr(dstacks[s]), 3 * self.views, B, H, W, _lib.stream_ptr())
             if on_done and s in (2, 0):      # shared stream nets: complete after the I (resp. H) stream
                 on_done('in_net_id' if s == 2 else 'in_net_hv')
+        return dstacks

@@ -8,6 +8,8 @@ On CUDA (= HIP on ROCm) tensors with four streams and model_ksize 2 or 3 the who
 kernels through the C ABI (engine.Trunk; 3x3 filters on the exact-f32 kernels whatever MMLF_CONV_MODE says), with
 BatchNorm (the default) and, for model_ksize 2, also under model_no_batchnorm (ReLU-only blocks: both ReLUs in the
 convolutions' epilogues, no BatchNorm launch); there is no fallback on that path: a missing libmmlf_hip.so raises.
+That path is differentiable in the parameters and in the four view stacks, like the reference's nn.Conv2d tree; a net whose
+parameters are all frozen is differentiated in its inputs without any weight-gradient launch (_TrunkFn).
 CPU tensors, and the flags the README recipes never use (model_cross, other kernel sizes, model_no_batchnorm together
 with model_ksize 3, model_unet), run the module tree with stock torch ops ("plumbing path": BASELINE.json configs[0],
 CPU tests, gloo rehearsal).
@@ -91,14 +93,19 @@ class _UNetTail(nn.Module):
 
 
 class _TrunkFn(torch.autograd.Function):
-    """One autograd node for in_net_hv x2, in_net_id x2, concat and out_net."""
+    """One autograd node for in_net_hv x2, in_net_id x2, concat and out_net: differentiable in the parameters and in the
+    four view stacks.  Backward forms what autograd asks for (ctx.needs_input_grad): the gradient of each stack that requires
+    one, as a (B, views, 3, H, W) tensor, and the parameter gradients only if some parameter requires one -- a frozen
+    network used as a differentiable function of its inputs pays for no weight gradient."""
 
     @staticmethod
     def forward(ctx, module, train, save, h, v, i, d, *params):
         p = module._tensor_dict()                       # buffers; parameters as passed (a replica's per-device copies)
         p.update(zip(module._param_names, (t.detach() for t in params)))
+        frozen = not any(ctx.needs_input_grad[7:])
         with torch.no_grad():
-            out, tape = module._trunk.forward(p, [h, v, i, d], train, save)
+            out, tape = module._trunk.forward(p, [h, v, i, d], train, save, input_grads=ctx.needs_input_grad[3:7],
+                                              frozen=frozen)
         ctx.module, ctx.tape, ctx.p = module, tape, (p if save else None)
         return out
 
@@ -109,15 +116,17 @@ class _TrunkFn(torch.autograd.Function):
             raise RuntimeError('FeedForward: backward through a forward that saved nothing')
         ctx.tape = ctx.p = None
         names = module._param_names
-        sizes = [p[n].numel() for n in names]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=gout.device)
-        grads, o = {}, 0
-        for n, sz in zip(names, sizes):
-            grads[n] = flat[o:o + sz].view_as(p[n])
-            o += sz
+        grads = None
+        if any(ctx.needs_input_grad[7:]):
+            sizes = [p[n].numel() for n in names]
+            flat = torch.zeros(sum(sizes), dtype=torch.float32, device=gout.device)
+            grads, o = {}, 0
+            for n, sz in zip(names, sizes):
+                grads[n] = flat[o:o + sz].view_as(p[n])
+                o += sz
         with torch.no_grad(), torch.cuda.device(gout.device):
-            module._trunk.backward(p, tape, gout, grads)
-        return (None, None, None, None, None, None, None) + tuple(grads[n] for n in names)
+            dstacks = module._trunk.backward(p, tape, gout, grads, input_grads=ctx.needs_input_grad[3:7])
+        return (None, None, None) + tuple(dstacks) + tuple(grads[n] if grads else None for n in names)
 
 
 class _HeadUprFn(torch.autograd.Function):
@@ -289,7 +298,7 @@ class FeedForward(nn.Module):
             params = [td[n] for n in self._param_names]
             if params[0].device != h_views.device:
                 raise ValueError(f'FeedForward: parameters on {params[0].device}, input on {h_views.device}')
-            save = torch.is_grad_enabled() and any(t.requires_grad for t in params)
+            save = torch.is_grad_enabled() and any(t.requires_grad for t in params + stacks)
             with torch.cuda.device(h_views.device):      # DataParallel worker threads: launch on the replica's device
                 output = _TrunkFn.apply(self, self.training, save, *stacks, *params)
         else:
