@@ -7,6 +7,8 @@ import ctypes
 import os
 import re
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MMLF_HIP_LIB selects another build of the same ABI (kernel A/B experiments); never a fallback
 LIB_PATH = os.environ.get('MMLF_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libmmlf_hip.so')
@@ -110,8 +112,8 @@ def load():
         # torch FIRST: it ships a HIP runtime of its own (torch/lib/libamdhip64.so) and this library is linked against the
         # system's (/opt/rocm/lib).  Loaded in the other order the process holds two runtimes and the first launch fails with
         # "no ROCm-capable device is detected" (seen when `python __graft_entry__.py smoke` loaded the library in build(), before
-        # anything had imported torch); with torch's runtime already mapped the loader resolves this library's dependency to it.
-        import torch  # noqa: F401
+        # anything had imported torch); with torch's runtime already mapped the loader resolves this library's dependency to it:
+        # this module imports torch at its top.
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
                 f'{LIB_PATH} not found: build it with `python -m mmlf_amd.csrc.build` '
@@ -151,6 +153,22 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def check(t, name, device, dtype=torch.float32, shape=None, numel=None, min_numel=None, contiguous=True):
+    """Hold a tensor that a caller supplied to what the kernel behind `ptr(t)` takes on trust: it lives on `device`, has
+    `dtype` (None: any, the caller converts) and the exact `shape`, exactly `numel` or at least `min_numel` elements, and is
+    contiguous.  Called where such a tensor enters the native path, ahead of the first launch: a raw pointer of another
+    device or a shorter tensor is a GPU memory fault, another dtype or stride order a quietly wrong result.  Reads the
+    tensor's metadata only (any device, `meta` included); never the pointer, never the library."""
+    ok = (t is not None and t.device == device and dtype in (None, t.dtype) and (shape is None or tuple(t.shape) == tuple(shape))
+          and (numel is None or t.numel() == numel) and (min_numel is None or t.numel() >= min_numel)
+          and (not contiguous or t.is_contiguous()))
+    if not ok:
+        found = 'None' if t is None else f'{t.dtype} {tuple(t.shape)} on {t.device}, contiguous={t.is_contiguous()}'
+        need = ', '.join(f'{k}={v}' for k, v in (('dtype', dtype), ('shape', shape if shape is None else tuple(shape)),
+                                                 ('numel', numel), ('min_numel', min_numel),
+                                                 ('contiguous', contiguous or None)) if v is not None)
+        raise ValueError(f'{name}: found {found}; required on {device}: {need}')
+
+
 def stream_ptr():
-    import torch
     return torch.cuda.current_stream().cuda_stream

@@ -12,7 +12,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import call, ptr
+from ._lib import call, check, ptr
 
 VAR_IDENTITY, VAR_TRANSPOSE, VAR_TRANSPOSE_FLIPH = 0, 1, 2
 BN_BLOCKS = 1024
@@ -479,6 +479,35 @@ class Trunk:
         self.out_blocks.append(BlockSpec(f'out_net.{out_blocks - 1}', c, oc, None))
         if chs % 2 or cs_of(c) != c:
             raise ValueError('native trunk needs an even model_chs with 4*model_chs a multiple of 8')
+        # state_dict key -> element count of every parameter and BatchNorm buffer the blocks read through raw pointers
+        # (check_params); h / v and i / d share their nets' keys
+        self._numel = {}
+        for spec in [b for _, _, blocks in self.streams for b in blocks] + self.out_blocks:
+            n = {'0.weight': spec.cout * spec.cin * ksize * ksize, '0.bias': spec.cout,
+                 '2.weight': spec.cout * spec.cout * ksize * ksize, '2.bias': spec.cout}
+            if spec.bn is True:
+                n.update({f'3.{k}': spec.cout for k in ('weight', 'bias', 'running_mean', 'running_var')})
+                n['3.num_batches_tracked'] = 1
+            self._numel.update({f'{spec.prefix}.{k}': v for k, v in n.items()})
+        self._grad_names = [n for n in self._numel if n.endswith(('.weight', '.bias'))]     # what backward accumulates into
+        self._checked = {}
+
+    def _check_dict(self, what, d, names, dev):
+        """every d[name]: present, on `dev`, contiguous, float32 (the BatchNorm counter int64), of the element count its block
+        implies.  Once per (data_ptr, device) signature, as _Workspace.packed_filters keeps its table: a training run's
+        parameters and gradient views keep their storage (Adam updates in place), so a step pays one pointer read per tensor."""
+        ts = [d.get(name) for name in names]
+        sig = (dev, *[t if t is None else (t.data_ptr(), t.device) for t in ts])
+        if self._checked.get(what) != sig:
+            for name, t in zip(names, ts):
+                check(t, f'{what}[{name!r}]', dev, torch.int64 if name.endswith('num_batches_tracked') else torch.float32,
+                      numel=self._numel[name])
+            self._checked[what] = sig
+
+    def check_params(self, p, dev):
+        """every parameter and buffer the trunk will read -- the pack kernels read an OIHW master filter through its raw
+        pointer, so a channels_last model is refused, like one on another device"""
+        self._check_dict('parameters', p, self._numel, dev)
 
     # ------------------------------------------------------------------ filters
     def _prepack(self, p, dev, with_dgrad, input_grads=None, fold=False):
@@ -652,7 +681,8 @@ class Trunk:
         return out, cs_out, None
 
     def forward(self, p, stacks, train, save, packed=None, input_grads=None, frozen=False):
-        """stacks: four (B, views, 3, H, W) contiguous float32 device tensors.
+        """stacks: four (B, views, 3, H, W) contiguous float32 device tensors.  They, the grid tensors of `packed` and every
+        entry of `p` the blocks read are validated here (_lib.check), ahead of the first call into the library.
         packed (instead of stacks): (Geometry, [four grid tensors of channel stride cs_of(3 views), with their amax arrays]) --
         inputs some other kernel already wrote in the grid layout (the Ensamble's mmlf_shift_pack).
         input_grads (with save): four bools, the streams whose input gradient backward will be asked for -- their first
@@ -661,17 +691,26 @@ class Trunk:
         with BatchNorm then runs the inference launches (BatchNorm folded into conv2) and keeps what a model_no_batchnorm
         forward keeps: the same output bits as without a tape, and a backward without any BatchNorm launch.
         Returns (output NCHW (B,oc,H,W), tape or None)."""
+        cin0 = self.views * 3
         if packed is not None:
             geo, xs_in = packed
             B, H, W = geo.B, geo.H, geo.W
             dev = xs_in[0].device
-            cin0 = self.views * 3
+            if geo.ksize != self.ksize or len(xs_in) != 4:
+                raise ValueError(f'Trunk.forward: packed= needs four grid tensors of a ksize {self.ksize} geometry')
+            for k, t in enumerate(xs_in):
+                check(t, f'packed[{k}]', dev, min_numel=geo.alloc * cs_of(cin0))
         else:
-            h = stacks[0]
-            B, n, c, H, W = h.shape
-            dev = h.device
+            shape = tuple(getattr(stacks[0], 'shape', ()))
+            if len(stacks) != 4 or len(shape) != 5 or shape[1:3] != (self.views, 3):
+                raise ValueError(f'Trunk.forward: four (B, {self.views}, 3, H, W) stacks required, the first has shape {shape}')
+            B, _, _, H, W = shape
+            dev = stacks[0].device
+            for name, t in zip('hvid', stacks):
+                check(t, f'{name}_views', dev, shape=shape)
+        self.check_params(p, dev)
+        if packed is None:
             geo = Geometry(B, H, W, self.ksize)
-            cin0 = n * c
         _Workspace.get(dev).enter_stream()
         # BatchNorm folded into conv2: inference, and the frozen evaluation that is differentiated in its inputs (3x3 trunks
         # have no ReLU-only backward and keep the unfolded form under a tape)
@@ -679,7 +718,7 @@ class Trunk:
         relu_only = not self.batchnorm or fold                  # every block below the head ends in conv2's own ReLU
         packs = self._prepack(p, dev, save, input_grads, fold)
         tracked = []                  # BatchNorm counters of this pass: ONE increment launch at its end
-        tape = {'geo': geo, 'streams': [], 'out': [], 'packs': packs}
+        tape = {'geo': geo, 'device': dev, 'streams': [], 'out': [], 'packs': packs}
         if packed is not None:
             concat, xs = geo.buf(4 * self.chs, dev), list(xs_in)
         else:
@@ -826,8 +865,10 @@ class Trunk:
         input_grads: four bools (streams H, V, I, D), the view stacks whose gradient is wanted; default none.  Returns a list
         of four entries: the (B, views, 3, H, W) float32 gradient of a wanted stack, None for the others.  The parameter
         gradients do not depend on it: the same weight-gradient launches in the same order."""
-        geo = tape['geo']
-        dev = grad_output.device
+        geo, dev = tape['geo'], tape['device']
+        check(grad_output, 'grad_output', dev, shape=(geo.B, self.oc, geo.H, geo.W), contiguous=False)
+        if grads is not None:
+            self._check_dict('grads', grads, self._grad_names, dev)
         _Workspace.get(dev).enter_stream()
         B, H, W = geo.B, geo.H, geo.W
         cs = cs_of(self.oc)

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import call, ptr
+from ._lib import call, check, ptr
 from .feed_forward import laplacian
 
 
@@ -62,6 +62,14 @@ def shift_views_torch(stacks, disp):
             x = t[..., k, :, :, :]
             t[..., k, :, :, :] = _roll(x, sign * int(s0), -2) * float(w0) + _roll(x, sign * int(s1), -2) * float(w1)
     return h, v, i, d
+
+
+def _fused_members(model, inner, views, c):
+    """whether the members take the fused path of _members_hip: the UPR model itself (not a wrapper; not with the DPP head,
+    whose mean is the arg-max one), native, in evaluation, outside autograd, on its own number of RGB views"""
+    return bool(FUSED_MEMBERS and model is inner and getattr(inner, '_native_ok', False) and getattr(inner, 'uncert', False)
+                and not getattr(inner, 'discrete', False) and not inner.training and not torch.is_grad_enabled()
+                and views == inner.views and c == 3)
 
 
 class Ensamble(nn.Module):
@@ -117,11 +125,9 @@ class Ensamble(nn.Module):
         b, views, c, hh, ww = h.shape
         S = len(disps)
         dev = h.device
-        for name, t in (('v_views', v), ('i_views', i), ('d_views', d)):
-            if t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != tuple(h.shape):
-                # raw pointers go to the shift kernel: a tensor of another device would fault inside it
-                raise ValueError(f'Ensamble: {name} must be a float32 tensor of shape {tuple(h.shape)} on {dev}, '
-                                 f'got {t.dtype} {tuple(t.shape)} on {t.device}')
+        for name, t in (('h_views', h), ('v_views', v), ('i_views', i), ('d_views', d)):
+            # raw pointers go to the shift kernels (any strides: each batch item is made contiguous below)
+            check(t, f'Ensamble: {name}', dev, shape=h.shape, contiguous=False)
         model = self.model
         inner = model.module if hasattr(model, 'module') else model
         tab_s, tab_w = shift_table(disps, views)
@@ -136,8 +142,9 @@ class Ensamble(nn.Module):
         # intermediate, no pack pass) and the members' UPR `posterior` -- 108 planes per member that ensamble.py:66-76 never
         # reads -- is not formed.  Same bits as the path below (tests/test_ensamble.py).  For the uncertainty model itself, in
         # evaluation, outside autograd; anything else (a DataParallel wrapper, another head) takes the module's own forward.
-        fused = (FUSED_MEMBERS and model is inner and getattr(inner, '_native_ok', False) and getattr(inner, 'uncert', False)
-                 and not inner.training and not torch.is_grad_enabled() and views == inner.views and c == 3)
+        fused = _fused_members(model, inner, views, c)
+        if fused:
+            inner._trunk.check_params(inner._tensor_dict(), dev)       # the trunk's own check, ahead of the first shear launch
         for bi in range(b):
             src = [t[bi].contiguous() for t in (h, v, i, d)]
             for s0 in range(0, S, chunk):

@@ -136,6 +136,8 @@ class _HeadUprFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, output, grid, steps):
+        if output.shape[1] < 2:
+            raise ValueError(f'UPR head: (mean, logvar) channels required, the output has {output.shape[1]}')
         o = output.detach().contiguous()
         b, _, hh, ww = o.shape
         posterior = torch.empty((b, steps, hh, ww), dtype=torch.float32, device=o.device)
@@ -163,6 +165,8 @@ class _HeadDppFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, scores, grid_torch, grid_np, steps):
+        if scores.shape[1] != steps:      # (model_uncert with model_discrete: two channels; the stock branch fails to broadcast)
+            raise RuntimeError(f'DPP head: {steps} score channels required (the kernel writes that many), got {scores.shape[1]}')
         sc = scores.detach().contiguous()
         b, _, hh, ww = sc.shape
         one_hot, posterior = torch.empty_like(sc), torch.empty_like(sc)
@@ -282,13 +286,9 @@ class FeedForward(nn.Module):
     def forward(self, h_views, v_views, i_views=None, d_views=None):
         b, n, c, hh, ww = h_views.shape
         if h_views.is_cuda and self._native_ok:
-            _lib.load()  # raises if the HIP library is missing: no silent fallback on the GPU path
+            # no silent fallback on the GPU path: Trunk.forward validates the stacks and the parameters (dtype, contiguity,
+            # device, extent), then loads the HIP library, which raises if it is missing
             stacks = [h_views, v_views, i_views, d_views]
-            for t in stacks:
-                if t is None or not t.is_contiguous() or t.dtype != torch.float32 or t.shape != h_views.shape:
-                    raise ValueError('FeedForward: four contiguous float32 (b, n, 3, h, w) stacks required')
-                if t.device != h_views.device:
-                    raise ValueError(f'FeedForward: stacks on different devices ({t.device} vs {h_views.device})')
             td = self._tensor_dict()
             missing = [n for n in self._param_names if n not in td]
             if missing:
@@ -296,9 +296,7 @@ class FeedForward(nn.Module):
                                    '(an unsupported kind of module copy?); use mmlf_amd.train.TrainStep for data '
                                    'parallelism (one process per GPU)')
             params = [td[n] for n in self._param_names]
-            if params[0].device != h_views.device:
-                raise ValueError(f'FeedForward: parameters on {params[0].device}, input on {h_views.device}')
-            save = torch.is_grad_enabled() and any(t.requires_grad for t in params + stacks)
+            save = torch.is_grad_enabled() and any(getattr(t, 'requires_grad', False) for t in params + stacks)
             with torch.cuda.device(h_views.device):      # DataParallel worker threads: launch on the replica's device
                 output = _TrunkFn.apply(self, self.training, save, *stacks, *params)
         else:

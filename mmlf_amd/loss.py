@@ -10,7 +10,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._lib import call, ptr
+from ._lib import call, check, ptr
 from .engine import LOSS_BLOCKS
 
 KIND_L1, KIND_UPR, KIND_CE = 0, 1, 2
@@ -29,13 +29,22 @@ def create_mask_margin(shape, margin=0):
     return mask
 
 
+def _check_loss_args(dev, n, oc, mask, grid_torch, den_override):
+    """what both fused losses take: the kernels walk n = B*H*W mask pixels (converted by the caller: any dtype, any strides),
+    oc grid entries and one float64 denominator -- a shorter tensor, or one of another device, is read past its end"""
+    check(mask, 'loss: mask', dev, None, numel=n, contiguous=False)
+    if grid_torch is not None:
+        check(grid_torch, 'loss: grid', dev, min_numel=oc)
+    if den_override is not None:
+        check(den_override, 'loss: den_override', dev, torch.float64, min_numel=1)
+
+
 def native_loss(kind, output, gt, mask, grid_torch=None, half_step=0.0, want_grad=True, den_override=None):
     """Fused loss on the raw trunk output (B,oc,H,W).  Returns (loss scalar tensor, grad or None)."""
     B, oc, H, W = output.shape
     dev = output.device
-    for name, t in (('target', gt), ('mask', mask), ('grid', grid_torch), ('den_override', den_override)):
-        if t is not None and t.device != dev:       # a raw pointer of another device would fault inside the kernel
-            raise ValueError(f'loss: {name} is on {t.device}, the model output on {dev}')
+    _check_loss_args(dev, B * H * W, oc, mask, grid_torch, den_override)
+    check(gt, 'loss: target', dev, None, numel=B * H * W, contiguous=False)
     output = output.contiguous()
     gt = gt.contiguous().float()
     mask = mask.contiguous().to(torch.int32)
@@ -55,10 +64,12 @@ def native_multi_loss(kind, output, target, mask, mask_padding=None, grid_torch=
     for KIND_UPR_PADDED.  Returns (loss scalar tensor, grad or None)."""
     B, oc, H, W = output.shape
     dev = output.device
-    for name, t in (('target', target), ('mask', mask), ('mask_padding', mask_padding), ('grid', grid_torch),
-                    ('den_override', den_override), ('aux_override', aux_override)):
-        if t is not None and t.device != dev:
-            raise ValueError(f'loss: {name} is on {t.device}, the model output on {dev}')
+    _check_loss_args(dev, B * H * W, oc, mask, grid_torch, den_override)
+    check(target, 'loss: target', dev, None, contiguous=False)        # (its shape: below, by kind)
+    if mask_padding is not None:
+        check(mask_padding, 'loss: mask_padding', dev, None, numel=B * H * W, contiguous=False)
+    if aux_override is not None:
+        check(aux_override, 'loss: aux_override', dev, torch.float64, min_numel=2)
     output = output.contiguous()
     target = target.contiguous().float()
     P = 0

@@ -7,7 +7,7 @@ and the CPU path are torch expressions."""
 import torch
 
 from . import _lib
-from ._lib import call, ptr
+from ._lib import call, check, ptr
 
 
 def _bin_edges(n_bins, x_min, x_max, device):
@@ -18,6 +18,7 @@ def _bin_edges(n_bins, x_min, x_max, device):
 def _lmm_hip(n_bins, x_min, x_max, means, logvars):
     """means, logvars: (S, B, H, W) float32 CUDA tensors -> (B, n_bins, H, W) float64."""
     S, B, H, W = means.shape
+    check(logvars, 'logvars', means.device, None, shape=means.shape, contiguous=False)      # (converted below)
     means, logvars = means.contiguous().float(), logvars.contiguous().float()
     edges = _bin_edges(n_bins, x_min, x_max, means.device)
     out = torch.empty((B, n_bins, H, W), dtype=torch.float64, device=means.device)
