@@ -87,7 +87,10 @@ int mmlf_pack_filter(const float *w_oihw, float *packed, int Cout, int Cin, int 
  *   out[q + out_shift][n] = valid(q) ? act(bias[n] + sum_t sum_k in[q + off_t][k] * Wp[t][k][n]) : 0
  * valid(q): q < B*G and y < vh and x < vw.  relu: fuse nn.ReLU (feed_forward.py:124).
  * relu_ref (nullable): multiply by (relu_ref[q + out_shift][n] > 0) -- ReLU backward fused into dgrad.
- * N_store channels are written per position (N_store <= cs_out; pad channels get 0). */
+ * N_store channels are written per position (N_store <= cs_out; pad channels get 0).
+ * N <= 512 in the three arithmetic variants: up to 288 output channels are one launch, wider layers run as two column
+ * blocks behind this interface (the packed filter then holds the blocks back to back; the size queries say how much).
+ * The weight gradient takes Cout <= 512 likewise; the 3x3 entry points stay at 288. */
 int mmlf_conv2x2(const float *in, int cs_in, int K, const float *packed, const float *bias, int N,
                  float *out, int cs_out, int N_store, int out_shift, int vh, int vw,
                  int B, int H, int W, int relu, const float *relu_ref, int cs_ref, void *stream);

@@ -30,6 +30,32 @@ extern "C" int mmlf_debug_oob_counts(unsigned long long *host8, int reset)
 #endif
 
 // ---------------------------------------------------------------------------------------------
+// Column blocks of the wide 2x2 layers (288 < N <= 512).  Such a layer is computed as TWO blocks of 160, 192
+// or 256 packed columns each (G = 10, 12, 16 sixteen-column groups; 320, 384 or 512 packed columns in all: nothing wasted at
+// N = 320, 384 and 512, an eighth at 448), by the kernel bodies the narrower layers run, one launch per block.  Block b owns
+// output channels [b * npb, (b + 1) * npb): its own packed filter (the blocks lie back to back, each a complete packed
+// filter of npb columns -- for the f16 split with its columns' unscale tail), its bias / output / reference offsets, its
+// range of the BatchNorm partials and its quarter (256 of every 512) of the transposed ReLU mask words.
+// wide_np is the ONE rule: the size queries, packing, the launches and the audit all go through it (x6_np / f32_np below),
+// and a packed-column total above 288 can only have come from it, which is how the packing kernels find a column's block.
+// ---------------------------------------------------------------------------------------------
+constexpr int MMLF_MAX_N = 288;          // packed columns of one launch
+constexpr int MMLF_MAX_N_WIDE = 512;     // ... of a layer in column blocks (2x2 filters)
+static inline int wide_np(int N)         // total packed columns of a wide layer
+{
+    if (N <= MMLF_MAX_N || N > MMLF_MAX_N_WIDE) return -1;
+    return N <= 320 ? 320 : N <= 384 ? 384 : 512;
+}
+__host__ __device__ static inline int col_blocks(int np_total) { return np_total > MMLF_MAX_N ? 2 : 1; }
+// packed column n of np_total -> its block, its column there, the block's columns
+__device__ __forceinline__ void col_block_of(int n, int np_total, int &blk, int &nl, int &npb)
+{
+    npb = np_total / col_blocks(np_total);
+    blk = n >= npb ? 1 : 0;
+    nl = n - blk * npb;
+}
+
+// ---------------------------------------------------------------------------------------------
 // filter packing, exact f32: OIHW master (Cout, Cin, KS, KS) -> [chunk][tap(KS*KS)][kh][NP][4] with k = 8*chunk + 4*kh + s.
 // dgrad = 1 packs the data gradient's filter: taps rotated by 180 degrees, Cin / Cout swapped.
 // ---------------------------------------------------------------------------------------------
@@ -53,7 +79,9 @@ __global__ void pack_filter_f32_kernel(const float *__restrict__ w, float *__res
         else { co = k; ci = n; tsrc = TAPS - 1 - t; }
         float v = 0.f;
         if (ci < Cin && co < Cout) v = w[((size_t)co * Cin + ci) * TAPS + master_tap<KS>(tsrc, variant)];
-        out[idx] = v;
+        int blk, nl, npb;                  // (one block: the linear index idx)
+        col_block_of(n, NP, blk, nl, npb);
+        out[(size_t)blk * nchunk * TAPS * 2 * npb * 4 + ((((size_t)c * TAPS + t) * 2 + kh) * npb + nl) * 4 + s] = v;
     }
 }
 
@@ -77,7 +105,8 @@ struct ConvArgs {
     Magic divP, divR;                    // q / P and row / R without integer division
     int R;
     double *bn_partial;                  // optional (f16 split): per-workgroup sums of out and out^2 per channel,
-                                         // [block][2][n_true] doubles, the input of the BatchNorm finalize
+                                         // [block][2][bn_stride] doubles, the input of the BatchNorm finalize
+    int bn_stride;                       // channels of the whole layer (= n_true unless the launch is a column block of it)
     unsigned *relu_mask_out;             // optional: (out > 0) as bits, [tile][wave][8 rows][64 lanes] words, bit = column block
     const unsigned *relu_mask_in;        // optional: such a mask instead of relu_ref (same launch geometry and N)
     // bytes the caller's buffers hold behind `out` / `ref` by the ABI's contract (mmlf_grid_alloc_positions): the epilogue's
@@ -159,11 +188,18 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &a, const f32x16 (&
 // column n (= output channel of the launch).  Every column carries its own power-of-two scale (its max |w|
 // goes to [2^14, 2^15)), so an output channel whose weights are small as a whole keeps its 22 bits;
 // unscale[n] = 1 / scale[n] is what the convolution's epilogue multiplies column n by.
-__device__ __forceinline__ void pack_filter_h2_column(const float *__restrict__ w, unsigned short *__restrict__ out,
+// `packed`: the filter's whole packed image, NP its packed columns in all: column n lies in a column block of its own
+// (col_block_of) whose planes are followed by its columns' unscale factors.
+__device__ __forceinline__ void pack_filter_h2_column(const float *__restrict__ w, void *__restrict__ packed,
                                                       int Cout, int Cin, int variant, int dgrad, int nchunk, int NP,
-                                                      float *__restrict__ unscale, int n, float *red)
+                                                      int n, float *red)
 {
     const int tid = threadIdx.x;
+    int blk, nl, npb;
+    col_block_of(n, NP, blk, nl, npb);
+    char *const base = reinterpret_cast<char *>(packed) + (size_t)blk * ((size_t)nchunk * 8 * npb * 16 + (size_t)npb * 4);
+    unsigned short *const out = reinterpret_cast<unsigned short *>(base);
+    float *const unscale = reinterpret_cast<float *>(base + (size_t)nchunk * 8 * npb * 16);
     const int K = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;
     auto at = [&](int k, int tap) -> size_t {      // OIHW index of (packed row k, column n, master tap)
         return dgrad ? ((size_t)k * Cin + n) * 4 + tap : ((size_t)n * Cin + k) * 4 + tap;
@@ -175,7 +211,7 @@ __device__ __forceinline__ void pack_filter_h2_column(const float *__restrict__ 
     if ((tid & 63) == 0) red[tid >> 6] = m;
     __syncthreads();
     const float sc = pow2_scale_for(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
-    if (tid == 0) unscale[n] = 1.f / sc;
+    if (tid == 0) unscale[nl] = 1.f / sc;
     for (int e = tid; e < 4 * nchunk; e += 256) {
         const int c = e >> 2, t = e & 3;
         const int tap = master_tap<2>(dgrad ? 3 - t : t, variant);
@@ -193,17 +229,16 @@ __device__ __forceinline__ void pack_filter_h2_column(const float *__restrict__ 
         vh.z = h[4] | (unsigned)h[5] << 16; vh.w = h[6] | (unsigned)h[7] << 16;
         vl.x = l[0] | (unsigned)l[1] << 16; vl.y = l[2] | (unsigned)l[3] << 16;
         vl.z = l[4] | (unsigned)l[5] << 16; vl.w = l[6] | (unsigned)l[7] << 16;
-        *reinterpret_cast<uint4 *>(out + ((((size_t)c * 2 + 0) * 4 + t) * NP + n) * 8) = vh;
-        *reinterpret_cast<uint4 *>(out + ((((size_t)c * 2 + 1) * 4 + t) * NP + n) * 8) = vl;
+        *reinterpret_cast<uint4 *>(out + ((((size_t)c * 2 + 0) * 4 + t) * npb + nl) * 8) = vh;
+        *reinterpret_cast<uint4 *>(out + ((((size_t)c * 2 + 1) * 4 + t) * npb + nl) * 8) = vl;
     }
 }
 
-__global__ __launch_bounds__(256) void pack_filter_h2_kernel(const float *__restrict__ w, unsigned short *__restrict__ out,
-                                                             int Cout, int Cin, int variant, int dgrad, int nchunk,
-                                                             int NP, float *__restrict__ unscale)
+__global__ __launch_bounds__(256) void pack_filter_h2_kernel(const float *__restrict__ w, void *__restrict__ packed,
+                                                             int Cout, int Cin, int variant, int dgrad, int nchunk, int NP)
 {
     __shared__ float red[4];
-    pack_filter_h2_column(w, out, Cout, Cin, variant, dgrad, nchunk, NP, unscale, blockIdx.x, red);
+    pack_filter_h2_column(w, packed, Cout, Cin, variant, dgrad, nchunk, NP, blockIdx.x, red);
 }
 
 // many filters, one launch: workgroup b packs column b - col0 of the filter whose column range holds b
@@ -218,9 +253,7 @@ __global__ __launch_bounds__(256) void pack_filters_h2_kernel(const mmlf_pack_de
     const mmlf_pack_desc d = table[lo];
     const int K = d.dgrad ? d.Cout : d.Cin;
     const int nchunk = (K + 7) / 8;
-    unsigned short *out = reinterpret_cast<unsigned short *>(d.packed);
-    float *tail = reinterpret_cast<float *>(reinterpret_cast<char *>(d.packed) + (size_t)nchunk * 8 * d.np * 16);
-    pack_filter_h2_column(d.w_oihw, out, d.Cout, d.Cin, d.variant, d.dgrad, nchunk, d.np, tail, (int)blockIdx.x - d.col0, red);
+    pack_filter_h2_column(d.w_oihw, d.packed, d.Cout, d.Cin, d.variant, d.dgrad, nchunk, d.np, (int)blockIdx.x - d.col0, red);
 }
 
 // split-precision filter packing: [chunk][plane(3)][tap(4)][NP][8 bf16], k = 8*chunk+j
@@ -244,8 +277,11 @@ __global__ void pack_filter_split_kernel(const float *__restrict__ w, unsigned s
         if (ci < Cin && co < Cout) v = w[((size_t)co * Cin + ci) * 4 + master_tap<2>(tsrc, variant)];
         unsigned p[3];
         split3(v, p[0], p[1], p[2]);
+        int blk, nl, npb;
+        col_block_of(n, NP, blk, nl, npb);
+        unsigned short *const ob = out + (size_t)blk * nchunk * 12 * npb * 8;
         for (int pl = 0; pl < 3; ++pl) {
-            out[((((size_t)c * 3 + pl) * 4 + t) * NP + n) * 8 + j] = (unsigned short)p[pl];
+            ob[((((size_t)c * 3 + pl) * 4 + t) * npb + nl) * 8 + j] = (unsigned short)p[pl];
         }
     }
 }
@@ -568,7 +604,7 @@ __device__ __forceinline__ ConvArgs late_args()
 // G <= 6 (narrow layers): VGPRs capped at 128 so that TWO workgroups share a CU -- with 60 short MFMAs
 // per wave per chunk the DMA latency of a single double-buffered workgroup is exposed.
 // G = number of 16-column output blocks (NP = 16*G packed columns): 2, 5 (the 70-channel layers: 80
-// columns instead of 96), 6, 7, 8 or 18.
+// columns instead of 96), 6, 7, 8 or 18; 10, 12 and 16 are the column blocks of the layers wider than 288 (wide_np).
 // PL = operand planes: 3 = bf16 3-way split, six passes ("bf16x6"); 2 = f16 2-way split of the scaled
 // operands, three passes ("f16x3").
 // NW = waves per workgroup = 32-position row groups per tile: 8 (256-position tiles) or, for the narrow layers on small
@@ -912,7 +948,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 16 || G <= 6 ? 4 : 2)) void conv4ta
             double t = 0.0;
 #pragma unroll
             for (int ww = 0; ww < NW; ++ww) t += stats_all[((size_t)ww * NP + ch) * 2 + which];
-            e.bn_partial[((size_t)blockIdx.x * 2 + which) * e.n_true + ch] = t;
+            e.bn_partial[((size_t)blockIdx.x * 2 + which) * e.bn_stride + ch] = t;
         }
     }
 #undef X6_DMA_PIECE
@@ -1096,7 +1132,7 @@ __global__ __launch_bounds__(512, 2) void conv4tap_rs_kernel(ConvArgs a, int ngr
             double t = 0.0;
 #pragma unroll
             for (int ww = 0; ww < 8; ++ww) t += stats_all[((size_t)ww * NP + ch) * 2 + which];
-            a.bn_partial[((size_t)blockIdx.x * 2 + which) * a.n_true + ch] = t;
+            a.bn_partial[((size_t)blockIdx.x * 2 + which) * a.bn_stride + ch] = t;
         }
     }
 }
@@ -1288,11 +1324,17 @@ __global__ __launch_bounds__(512) void conv9tap_kernel(ConvArgs a, int ncb, int 
 extern "C" int mmlf_conv_cus(void) { return device_cus(); }
 
 // exact-f32 packed filters of both sizes (ks = 2 or 3): [chunk][tap(ks*ks)][kh(2)][NP][4] floats
-static int64_t packed_filter_f32_floats(int ks, int K, int N)
+// packed columns of the exact-f32 kernels: pick_nt's 32-column tiles, and for 2x2 filters the column blocks above 288
+static inline int f32_np(int ks, int N)
 {
     const int nt = pick_nt(N);
-    if (nt < 0 || K <= 0) return -1;
-    return (int64_t)((K + 7) / 8) * ks * ks * 2 * (nt * 32) * 4;
+    return nt > 0 ? nt * 32 : (ks == 2 ? wide_np(N) : -1);
+}
+static int64_t packed_filter_f32_floats(int ks, int K, int N)
+{
+    const int np = f32_np(ks, N);
+    if (np < 0 || K <= 0) return -1;
+    return (int64_t)((K + 7) / 8) * ks * ks * 2 * np * 4;
 }
 
 static int pack_filter_f32(const char *who, int ks, const float *w, float *packed, int Cout, int Cin, int variant,
@@ -1302,9 +1344,9 @@ static int pack_filter_f32(const char *who, int ks, const float *w, float *packe
     MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "%s: bad variant %d", who, variant);
     MMLF_CHECK_ARG(Cout > 0 && Cin > 0, "%s: bad channels %d x %d", who, Cout, Cin);
     const int K = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;
-    const int nt = pick_nt(N);
-    MMLF_CHECK_ARG(nt > 0, "%s: N=%d not supported (max 288)", who, N);
-    const int nchunk = (K + 7) / 8, NP = nt * 32;
+    const int NP = f32_np(ks, N);
+    MMLF_CHECK_ARG(NP > 0, "%s: N=%d not supported (max %d)", who, N, ks == 2 ? MMLF_MAX_N_WIDE : MMLF_MAX_N);
+    const int nchunk = (K + 7) / 8;
     const long long total = (long long)nchunk * ks * ks * 2 * NP * 4;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
@@ -1345,7 +1387,7 @@ static int conv_common_args(const char *who, int ks, int np, ConvArgs &a, Grid &
     MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
     MMLF_CHECK_ARG(cs_in > 0 && cs_in % 8 == 0, "%s: cs_in=%d must be a multiple of 8", who, cs_in);
     MMLF_CHECK_ARG(K > 0 && (K + 7) / 8 * 8 == cs_in, "%s: K=%d does not match cs_in=%d", who, K, cs_in);
-    MMLF_CHECK_ARG(np > 0, "%s: N=%d not supported (max 288)", who, N);
+    MMLF_CHECK_ARG(np > 0, "%s: N=%d not supported (max %d)", who, N, ks == 2 ? MMLF_MAX_N_WIDE : MMLF_MAX_N);
     MMLF_CHECK_ARG(N_store > 0 && N_store <= cs_out && N_store <= np, "%s: N_store=%d vs cs_out=%d NP=%d", who,
                    N_store, cs_out, np);
     g = make_grid(B, H, W);
@@ -1359,6 +1401,31 @@ static int conv_common_args(const char *who, int ks, int np, ConvArgs &a, Grid &
     a.divP = make_magic((unsigned)g.P); a.divR = make_magic((unsigned)g.R);
     conv_buffer_bytes(a, g, ks == 3 ? grid_alloc_positions_k3(g) : grid_alloc_positions(g));
     return 0;
+}
+
+// Column block b of a wide 2x2 layer (wide_np): the launch arguments of the whole layer `a`, narrowed to the block's npb
+// packed columns.  packed_block_bytes: what one block's packed filter takes; unscale_off: where its columns' unscale factors
+// start in it (f16 split) or -1.  False: the block stores nothing (a channel slice that ends in front of it).
+static bool conv_block_args(const ConvArgs &a, int b, int npb, size_t packed_block_bytes, long long unscale_off, ConvArgs &ab)
+{
+    ab = a;
+    const int c0 = b * npb;
+    if (a.n_store <= c0) return false;
+    ab.n_store = a.n_store - c0 < npb ? a.n_store - c0 : npb;
+    ab.n_true = a.n_true - c0 < npb ? a.n_true - c0 : npb;
+    const char *wp = reinterpret_cast<const char *>(a.wp) + (size_t)b * packed_block_bytes;
+    ab.wp = reinterpret_cast<const float *>(wp);
+    ab.w_unscale = unscale_off >= 0 ? reinterpret_cast<const float *>(wp + unscale_off) : nullptr;
+    if (a.bias) ab.bias = a.bias + c0;
+    ab.out = a.out + c0;
+    ab.out_bytes = a.out_bytes - 4ll * c0;
+    if (a.ref) { ab.ref = a.ref + c0; ab.ref_bytes = a.ref_bytes - 4ll * c0; }
+    if (a.bn_partial) ab.bn_partial = a.bn_partial + c0;
+    // transposed mask words: 2 x 2 words per lane and block (G <= 16), i.e. 256 of the 512 words of a (tile, wave)
+    if (a.relu_mask_out) ab.relu_mask_out = a.relu_mask_out + 256 * b;
+    if (a.relu_mask_in) ab.relu_mask_in = a.relu_mask_in + 256 * b;
+    ab.mask_words = a.mask_words - 256 * b;
+    return true;
 }
 
 // ncb column blocks of NT*32 columns per tile (2x2: always one)
@@ -1382,28 +1449,40 @@ extern "C" int mmlf_conv2x2(const float *in, int cs_in, int K, const float *pack
                             float *out, int cs_out, int N_store, int out_shift, int vh, int vw, int B, int H,
                             int W, int relu, const float *relu_ref, int cs_ref, void *stream)
 {
-    const int nt = pick_nt(N);
+    const int np = f32_np(2, N);
     ConvArgs a;
     Grid g;
-    if (conv_common_args("mmlf_conv2x2", 2, nt * 32, a, g, in, cs_in, K, packed, bias, N, out, cs_out, N_store, out_shift, vh,
+    if (conv_common_args("mmlf_conv2x2", 2, np, a, g, in, cs_in, K, packed, bias, N, out, cs_out, N_store, out_shift, vh,
                          vw, B, H, W, relu, relu_ref, cs_ref))
         return 1;
     const long long ntiles = g.NQpad / MMLF_TILE;
     hipStream_t st = (hipStream_t)stream;
-    switch (nt) {
-    case 1: return launch_conv_f32<2, 1>(a, ntiles, 1, st);
-    case 3: return launch_conv_f32<2, 3>(a, ntiles, 1, st);
-    case 4: return launch_conv_f32<2, 4>(a, ntiles, 1, st);
-    default: return launch_conv_f32<2, 9>(a, ntiles, 1, st);
+    const int ncb = col_blocks(np), npb = np / ncb;
+    for (int b = 0; b < ncb; ++b) {
+        ConvArgs ab = a;
+        if (ncb > 1 && !conv_block_args(a, b, npb, (size_t)a.nchunk * 4 * 2 * npb * 4 * sizeof(float), -1, ab)) continue;
+        int rc;
+        switch (npb / 32) {
+        case 1: rc = launch_conv_f32<2, 1>(ab, ntiles, 1, st); break;
+        case 3: rc = launch_conv_f32<2, 3>(ab, ntiles, 1, st); break;
+        case 4: rc = launch_conv_f32<2, 4>(ab, ntiles, 1, st); break;
+        case 5: rc = launch_conv_f32<2, 5>(ab, ntiles, 1, st); break;
+        case 6: rc = launch_conv_f32<2, 6>(ab, ntiles, 1, st); break;
+        case 8: rc = launch_conv_f32<2, 8>(ab, ntiles, 1, st); break;
+        default: rc = launch_conv_f32<2, 9>(ab, ntiles, 1, st); break;
+        }
+        if (rc) return rc;
     }
+    return 0;
 }
 
 // ------------------------------------------------------------------ split-bf16 ("bf16x6") entry points
 // Packed column count NP of the split forward/dgrad kernels: 32, 80, then 16-column granularity up to
-// 128, then 288.  Packing and launch pick by this one rule, so the layouts always agree.
+// 128, then 288; above that the column blocks of wide_np.  Packing and launch pick by this one rule, so the layouts always agree.
 static inline int x6_np(int N)
 {
-    if (N <= 0 || N > 288) return -1;
+    if (N > MMLF_MAX_N) return wide_np(N);
+    if (N <= 0) return -1;
     if (N <= 32) return 32;
     if (N <= 80) return 80;
     if (N <= 128) return (N + 15) / 16 * 16;
@@ -1424,7 +1503,7 @@ extern "C" int mmlf_pack_filter_split(const float *w, void *packed, int Cout, in
     MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_pack_filter_split: bad variant %d", variant);
     const int K = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;
     const int NP = x6_np(N);
-    MMLF_CHECK_ARG(NP > 0, "mmlf_pack_filter_split: N=%d not supported (max 288)", N);
+    MMLF_CHECK_ARG(NP > 0, "mmlf_pack_filter_split: N=%d not supported (max %d)", N, MMLF_MAX_N_WIDE);
     const int nchunk = (K + 7) / 8;
     const long long total = (long long)nchunk * 32 * NP;
     int blocks = (int)((total + 255) / 256);
@@ -1572,6 +1651,28 @@ static int launch_conv_x6s(const ConvArgs &a, long long ntiles, hipStream_t st)
             return launch_conv_x6s_epi<G, PL, EPI_REF_IN>(a, n, st);
         MMLF_CONV_KIND_SWITCH(launch_conv_x6s_epi, G == 18, G != 18 || a.seg_delta == 0, G, PL);
     }
+    if constexpr (PL == 2 && (G == 10 || G == 12 || G == 16)) {
+        // Column blocks of a wide layer: the launch kinds of a training step get their own builds, as on the 280-wide layer (the
+        // generic G = 16 build spills).  The transposed form at every pitch, and ReLU mask words in that form ONLY: its 2 x 2
+        // words per lane let the two blocks share a tile's 4096 words, conv_epilogue16's eight words per lane do not.
+        const long long n = ntiles;
+        const int kind = (a.relu ? EPI_RELU : 0) | (a.bn_partial ? EPI_STATS : 0) | (a.relu_mask_in ? EPI_BITS_IN : 0) |
+                         (a.ref ? EPI_REF_IN : 0) | (a.relu_mask_out ? EPI_MASK_OUT : 0);
+        const bool tr = conv_tr_enabled() && conv_tr_fits(a);
+        if ((a.relu_mask_in || a.relu_mask_out) && !tr)
+            return mmlf_fail("mmlf_conv2x2_h2: N > %d keeps ReLU mask words in the transposed layout only (n_store %% 4 == 0, a "
+                             "16-byte aligned output, MMLF_CONV_TR not 0)", MMLF_MAX_N);
+        switch (kind) {
+        case EPI_PLAIN: if (tr) return launch_conv_x6s_epi<G, PL, EPI_PLAIN, true>(a, n, st); break;
+        case EPI_RELU: if (tr) return launch_conv_x6s_epi<G, PL, EPI_RELU, true>(a, n, st); break;
+        case EPI_RELU | EPI_MASK_OUT: return launch_conv_x6s_epi<G, PL, EPI_RELU | EPI_MASK_OUT, true>(a, n, st);
+        case EPI_BITS_IN: return launch_conv_x6s_epi<G, PL, EPI_BITS_IN, true>(a, n, st);
+        case EPI_STATS: return launch_conv_x6s_epi<G, PL, EPI_STATS>(a, n, st);
+        case EPI_REF_IN: return launch_conv_x6s_epi<G, PL, EPI_REF_IN>(a, n, st);
+        default: break;
+        }
+        if (a.relu_mask_in || a.relu_mask_out) return mmlf_fail("mmlf_conv2x2_h2: N > %d: this combination of ReLU mask options has no build", MMLF_MAX_N);
+    }
     // (other widths: the generic build, whose mask words have conv_epilogue16's layout for producer and consumer alike)
     return launch_conv_x6s_epi<G, PL, EPI_GENERIC>(a, ntiles, st);
 }
@@ -1585,6 +1686,9 @@ static int launch_conv_split(int np, const ConvArgs &a, long long ntiles, hipStr
     case 96: return launch_conv_x6s<6, PL>(a, ntiles, st);
     case 112: return launch_conv_x6s<7, PL>(a, ntiles, st);
     case 128: return launch_conv_x6s<8, PL>(a, ntiles, st);
+    case 160: return launch_conv_x6s<10, PL>(a, ntiles, st);      // (160, 192, 256: column blocks of a wide layer)
+    case 192: return launch_conv_x6s<12, PL>(a, ntiles, st);
+    case 256: return launch_conv_x6s<16, PL>(a, ntiles, st);
     default: return launch_conv_x6s<18, PL>(a, ntiles, st);
     }
 }
@@ -1605,12 +1709,12 @@ static int conv_split_impl(const char *who, int planes, const float *in, int cs_
     MMLF_CHECK_ARG((long long)cs_in * 4 * 64 < (1ll << 31), "%s: cs_in too large", who);
     MMLF_CHECK_ARG(planes == 3 || in_amax, "%s: the f16 split needs the input's max |x|", who);
     MMLF_CHECK_ARG(!bn_partial || (planes == 2 && N_store >= N), "%s: BatchNorm statistics need the f16 split path", who);
-    a.in_amax = in_amax; a.out_amax = out_amax; a.bn_partial = bn_partial;
+    a.in_amax = in_amax; a.out_amax = out_amax; a.bn_partial = bn_partial; a.bn_stride = N;
     a.relu_mask_out = relu_mask_out; a.relu_mask_in = relu_mask_in;
-    // the f16-packed filter ends with its columns' unscale factors
-    a.w_unscale = planes == 2 ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(packed) +
-                                                                  (size_t)(cs_in / 8) * 8 * np * 16)
-                              : nullptr;
+    const int ncb = col_blocks(np), npb = np / ncb;
+    // the f16-packed filter (of a column block) ends with its columns' unscale factors
+    const size_t plane_bytes = (size_t)(cs_in / 8) * (planes == 2 ? 8 : 12) * npb * 16;
+    a.w_unscale = planes == 2 ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(packed) + plane_bytes) : nullptr;
     a.nw = conv_sixteen_waves(planes, np, g) ? 16 : 8;
     const int tile = 32 * a.nw;
     if (g.P + tile + 1 <= 640) {   // one contiguous window of tile + 1 + P positions
@@ -1621,7 +1725,14 @@ static int conv_split_impl(const char *who, int planes, const float *in, int cs_
     a.a_tail = (a.seg_delta ? 257 : g.P + tile + 1) - 32 * (a.a_per_seg - 1);
     const long long ntiles = g.NQpad / tile;
     hipStream_t st = (hipStream_t)stream;
-    return planes == 3 ? launch_conv_split<3>(np, a, ntiles, st) : launch_conv_split<2>(np, a, ntiles, st);
+    for (int b = 0; b < ncb; ++b) {      // one launch; a wide layer: one per column block, same tiles and workgroups
+        ConvArgs ab = a;
+        if (ncb > 1 && !conv_block_args(a, b, npb, plane_bytes + (planes == 2 ? (size_t)npb * 4 : 0), planes == 2 ? (long long)plane_bytes : -1, ab))
+            continue;
+        const int rc = planes == 3 ? launch_conv_split<3>(npb, ab, ntiles, st) : launch_conv_split<2>(npb, ab, ntiles, st);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 extern "C" int mmlf_conv2x2_split(const float *in, int cs_in, int K, const void *packed, const float *bias, int N,
@@ -1647,12 +1758,11 @@ extern "C" int mmlf_pack_filter_h2(const float *w, void *packed, int Cout, int C
     MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_pack_filter_h2: bad variant %d", variant);
     const int K = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;
     const int NP = x6_np(N);
-    MMLF_CHECK_ARG(NP > 0, "mmlf_pack_filter_h2: N=%d not supported (max 288)", N);
+    MMLF_CHECK_ARG(NP > 0, "mmlf_pack_filter_h2: N=%d not supported (max %d)", N, MMLF_MAX_N_WIDE);
     const int nchunk = (K + 7) / 8;
-    // the per-column unscale factors sit behind the packed planes
-    float *tail = reinterpret_cast<float *>(reinterpret_cast<char *>(packed) + (size_t)nchunk * 8 * NP * 16);
-    hipLaunchKernelGGL(pack_filter_h2_kernel, dim3(NP), dim3(256), 0, (hipStream_t)stream, w, (unsigned short *)packed,
-                       Cout, Cin, variant, dgrad, nchunk, NP, tail);
+    // (the per-column unscale factors sit behind the packed planes of their column block)
+    hipLaunchKernelGGL(pack_filter_h2_kernel, dim3(NP), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin, variant, dgrad,
+                       nchunk, NP);
     return mmlf_launch_status("mmlf_pack_filter_h2");
 }
 
@@ -1689,7 +1799,7 @@ extern "C" int mmlf_conv2x2_blocks(int K, int N, int B, int H, int W)
     const Grid g = make_grid(B, H, W);
     const int nw = conv_sixteen_waves(2, np, g) ? 16 : 8;
     if (conv_rs_shape(2, np, (K + 7) / 8, nw)) return (int)conv_rs_blocks(g.NQpad / 32);
-    return (int)conv_split_blocks(np / 16, g.NQpad / (32 * nw), nw);
+    return (int)conv_split_blocks(np / col_blocks(np) / 16, g.NQpad / (32 * nw), nw);      // (column blocks: the same grid each)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1865,6 +1975,9 @@ extern "C" const char *mmlf_build_info(void)
 //    kernel reads positions Q0 + 32 w + 16 mb + r16 + {0, 1, P, P + 1}: the same end.  Output: position q + out_shift,
 //    q < NQpad, n_store channels; the ReLU reference likewise.  Row maxima: rows up to the one behind the last position
 //    read (input) / written (output).  Mask words: [tile][8][8][64].  Statistics: [workgroup][2][N] doubles.
+//    A layer wider than 288 columns is two launches of this kind on column blocks (wide_np): the same tiles, windows and
+//    workgroup count each, the packed filter's blocks back to back (the same byte total), the blocks' channels side by side
+//    in out / ref / bias / the statistics, and each block's mask words inside its tile's 4096: the ends below hold as they are.
 //  weight gradient: chunk c stages in[32 c .. 32 c + 32 + P] and g[32 c + g_shift .. + 31], c < NQpad / 32.
 // ---------------------------------------------------------------------------------------------
 extern "C" int mmlf_audit_conv_h2(int cs_in, int K, int N, int cs_out, int N_store, int out_shift, int cs_ref, int B, int H, int W,

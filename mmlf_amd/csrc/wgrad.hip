@@ -26,6 +26,7 @@ struct WgradArgs {
     float *part;          // [nsplit][4][CIP][NP]
     long long NQpad;
     int cs_in, cin, cs_g, g_shift, P, nsplit, nslice, chunks_per_split, nchunks;
+    int g_cols;           // channels of a row of g from the pointer on: cs_g, less the offset of a column block (wgrad_impl)
     const float *in_amax, *g_amax;   // f16 split: amax arrays of in and g (common.h)
     const float *chunk_scales;       // f16 split: [nchunks][2] power-of-two operand scales (wgrad_chunk_scales_kernel)
     long long in_bytes, g_bytes, part_floats;   // what the buffers hold by the ABI's contract: the wide kernel's staging loads are
@@ -135,7 +136,7 @@ __device__ __forceinline__ void wgrad_f32_taps(const WgradArgs &a)
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (KS == 2 || idx < G_F4) {
                 const int row = idx / (NP / 4), f = idx - row * (NP / 4);
-                if (4 * f < a.cs_g) v = *reinterpret_cast<const float4 *>(a.g + (size_t)(Qg + row) * a.cs_g + 4 * f);
+                if (4 * f < a.g_cols) v = *reinterpret_cast<const float4 *>(a.g + (size_t)(Qg + row) * a.cs_g + 4 * f);
             }
             rg[j] = v;
         }
@@ -405,7 +406,7 @@ __global__ __launch_bounds__(256, 2) void wgrad4tap_x6n_kernel(WgradArgs a)
         _Pragma("unroll") for (int j = 0; j < NG; ++j) {                                                    \
             const int idx = min(tid + 256 * j, WG_KQ * FG - 1);                                             \
             const int row = idx / FG, f = idx - row * FG;                                                   \
-            const int gc = min(4 * f, a.cs_g - 4);                                                          \
+            const int gc = min(4 * f, a.g_cols - 4);                                                        \
             MMLF_OOB(OOB_WG_G, ((Qc + a.g_shift + row) * a.cs_g + gc + 4) * 4ll > a.g_bytes);               \
             rg[j] = *reinterpret_cast<const float4 *>(a.g + (size_t)(Qc + a.g_shift + row) * a.cs_g + gc);  \
         }                                                                                                   \
@@ -500,7 +501,7 @@ __global__ __launch_bounds__(256, 2) void wgrad4tap_x6n_kernel(WgradArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------
-// wide-layer weight gradient (Cout <= 288): 512 threads = 8 waves, wave w = (tap w&3, column half w>>2).
+// wide-layer weight gradient (128 < Cout <= 288, and the first 288 columns of a wider layer): 512 threads = 8 waves, wave w = (tap w&3, column half w>>2).
 // A workgroup owns a slice of 16*MB input channels x all 288 columns and a split of the positions; the
 // LDS image is DOUBLE-buffered: while chunk c is multiplied, the registers holding chunk c+1 (loaded
 // from global memory one iteration earlier) are split and stored into the other buffer between the
@@ -576,7 +577,7 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
     for (int j = 0; j < NG; ++j) {
         const int idx = min(tid + 512 * j, WG_KQ * FG - 1);
         const int row = idx / FG, f = idx - row * FG;
-        gg_off[j] = (unsigned)((a.g_shift + row) * a.cs_g + min(4 * f, a.cs_g - 4)) * 4u;
+        gg_off[j] = (unsigned)((a.g_shift + row) * a.cs_g + min(4 * f, a.g_cols - 4)) * 4u;
         lg_off[j] = A_BYTES + row * ROWG + 8 * f;
     }
     const char *const in_b = reinterpret_cast<const char *>(a.in), *const g_b = reinterpret_cast<const char *>(a.g);
@@ -855,9 +856,23 @@ static inline bool wgrad16_cfg(int Cin, int Cout, long long nchunks, Wgrad16Cfg 
     return true;
 }
 
+// Column blocks of the gradient tensor (288 < Cout <= 512): the first 288 output channels, then the rest, each block a
+// launch of its own on the kernel its width takes by wgrad16_cfg / pick_nt, followed by its own reduction into its rows of the
+// OIHW master (co is the slowest index there: the blocks' rows do not interleave).  The launches run one after the other on
+// one stream and share the partial-sum region, which is sized by the larger block.  (The convolutions' packed layouts
+// have a block rule of their own, conv.hip wide_np: this kernel reads the unpacked gradient, so nothing ties the two.)
+constexpr int WGRAD_MAX_COUT = 288, WGRAD_MAX_COUT_WIDE = 512;
+static inline int wgrad_col_blocks(int Cout) { return Cout > WGRAD_MAX_COUT ? 2 : 1; }
+static inline int wgrad_block_cout(int Cout, int b) { return b == 0 ? (Cout < WGRAD_MAX_COUT ? Cout : WGRAD_MAX_COUT) : Cout - WGRAD_MAX_COUT; }
+
 // partial sums of the position splits (largest of the kernels' layouts)
 static int64_t wgrad_partial_floats(int Cin, int Cout)
 {
+    if (Cout > WGRAD_MAX_COUT) {
+        if (Cout > WGRAD_MAX_COUT_WIDE) return -1;
+        const int64_t n0 = wgrad_partial_floats(Cin, wgrad_block_cout(Cout, 0)), n1 = wgrad_partial_floats(Cin, wgrad_block_cout(Cout, 1));
+        return n0 > n1 ? n0 : n1;
+    }
     const int nt = pick_nt(Cout);
     if (nt < 0) return -1;
     const int nslice = (Cin + 1 + 31) / 32;
@@ -930,7 +945,7 @@ static WgradArgs wgrad_args(const float *in, int cs_in, int Cin, const float *g,
 {
     WgradArgs a = {};
     a.in = in; a.g = g; a.part = workspace; a.NQpad = gr.NQpad;
-    a.cs_in = cs_in; a.cin = Cin; a.cs_g = cs_g; a.g_shift = g_shift; a.P = gr.P;
+    a.cs_in = cs_in; a.cin = Cin; a.cs_g = a.g_cols = cs_g; a.g_shift = g_shift; a.P = gr.P;
     a.in_bytes = alloc * cs_in * 4; a.g_bytes = alloc * cs_g * 4;
     a.part_floats = part_floats;
     a.nchunks = (int)(gr.NQpad / WG_KQ);
@@ -1011,8 +1026,7 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
     MMLF_CHECK_ARG(in && g && gw && workspace, "mmlf_conv2x2_wgrad: null pointer");
     MMLF_CHECK_ARG(cs_in % 4 == 0 && cs_g % 4 == 0, "mmlf_conv2x2_wgrad: strides must be multiples of 4");
     MMLF_CHECK_ARG(Cin > 0 && Cin <= cs_in && Cout > 0 && Cout <= cs_g, "mmlf_conv2x2_wgrad: channels vs strides");
-    const int nt = pick_nt(Cout);
-    MMLF_CHECK_ARG(nt > 0, "mmlf_conv2x2_wgrad: Cout=%d not supported", Cout);
+    MMLF_CHECK_ARG(Cout <= WGRAD_MAX_COUT_WIDE, "mmlf_conv2x2_wgrad: Cout=%d not supported (max %d)", Cout, WGRAD_MAX_COUT_WIDE);
     MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_conv2x2_wgrad: bad variant");
     Grid gr = make_grid(B, H, W);
     MMLF_CHECK_ARG(g_shift >= 0 && g_shift <= gr.P + 1, "mmlf_conv2x2_wgrad: g_shift=%d", g_shift);
@@ -1031,13 +1045,24 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
         hipLaunchKernelGGL(wgrad_chunk_scales_kernel, dim3((a.nchunks + 255) / 256), dim3(256), 0, st, ca);
         a.chunk_scales = ca.out;
     }
-    if (planes && wgrad16_cfg(Cin, Cout, a.nchunks, &c)) {
-        wgrad_set_grid(a, c.nslice, c.nsplit);
-        const int rc = planes == 3 ? launch_wgrad_split<3>(c, a, st) : launch_wgrad_split<2>(c, a, st);
+    const WgradArgs whole = a;
+    for (int b = 0, c0 = 0; b < wgrad_col_blocks(Cout); c0 += wgrad_block_cout(Cout, b), ++b) {
+        // column block b: output channels [c0, c0 + cb) of g, rows c0 .. of the OIHW master and of the bias gradient
+        const int cb = wgrad_block_cout(Cout, b);
+        a = whole;
+        a.g = g + c0; a.g_cols = cs_g - c0; a.g_bytes = whole.g_bytes - 4ll * c0;
+        float *gwb = gw + (size_t)c0 * Cin * 4, *gbb = gb ? gb + c0 : nullptr;
+        int rc;
+        if (planes && wgrad16_cfg(Cin, cb, a.nchunks, &c)) {
+            wgrad_set_grid(a, c.nslice, c.nsplit);
+            rc = planes == 3 ? launch_wgrad_split<3>(c, a, st) : launch_wgrad_split<2>(c, a, st);
+            if (!rc) rc = wgrad_reduce<2>(a, gwb, gbb, Cin, cb, a.nslice * 16 * c.mb, 16 * c.nb, variant, accumulate, st);
+        } else {
+            rc = wgrad_f32<2>(a, pick_nt(cb), gwb, gbb, Cin, cb, variant, accumulate, st);
+        }
         if (rc) return rc;
-        return wgrad_reduce<2>(a, gw, gb, Cin, Cout, a.nslice * 16 * c.mb, 16 * c.nb, variant, accumulate, st);
     }
-    return wgrad_f32<2>(a, nt, gw, gb, Cin, Cout, variant, accumulate, st);
+    return 0;
 }
 
 // weight + bias gradient of a thin convolution: wave-private sums over its positions, reduced by wgrad_reduce_kernel.
@@ -1155,13 +1180,19 @@ extern "C" int mmlf_audit_wgrad_h2(int cs_in, int Cin, int cs_g, int Cout, int g
     MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0 && ends && Cin > 0 && Cout > 0, "mmlf_audit_wgrad_h2: bad argument");
     const Grid g = make_grid(B, H, W);
     const long long nchunks = g.NQpad / WG_KQ;
-    MMLF_CHECK_ARG(wgrad16_cfg(Cin, Cout, nchunks, &c), "mmlf_audit_wgrad_h2: Cout=%d", Cout);
+    MMLF_CHECK_ARG(Cout <= WGRAD_MAX_COUT_WIDE, "mmlf_audit_wgrad_h2: Cout=%d", Cout);
+    int64_t part = 0;                                                         // partial sums of the largest column block's launch
+    for (int b = 0; b < wgrad_col_blocks(Cout); ++b) {
+        MMLF_CHECK_ARG(wgrad16_cfg(Cin, wgrad_block_cout(Cout, b), nchunks, &c), "mmlf_audit_wgrad_h2: Cout=%d", Cout);
+        const int64_t n = (int64_t)c.nsplit * 4 * (c.nslice * 16 * c.mb) * (16 * c.nb);
+        part = n > part ? n : part;
+    }
     const long long last_c = (nchunks - 1) * WG_KQ;
     ends[0] = (last_c + g.P + 32 + 1) * cs_in * 4;                            // in: segment 1, row 32
     ends[1] = (last_c + g_shift + 31 + 1) * cs_g * 4;                         // g
     ends[2] = (int64_t)Cout * Cin * 4 * 4;                                    // gw (OIHW)
     ends[3] = (int64_t)Cout * 4;                                              // gb
-    ends[4] = ((int64_t)c.nsplit * 4 * (c.nslice * 16 * c.mb) * (16 * c.nb)   // workspace: partial sums of this launch ...
+    ends[4] = (part                                                           // workspace: partial sums of this launch ...
                > wgrad_partial_floats(Cin, Cout) ? -1                           // (must fit the sized region: else the scales overlap them)
                : wgrad_partial_floats(Cin, Cout) + 2 * nchunks + 2) * 4;        // ... then the per-chunk and the two tensor scales
     ends[5] = (MMLF_AMAX_HEAD + amax_rows(g)) * 4;                            // in_amax (the scale kernel clamps rows to amax_rows - 1)

@@ -19,6 +19,14 @@ BN_BLOCKS = 1024
 LOSS_BLOCKS = 1024
 
 
+# widest layer (output channels) of the convolution and weight-gradient entry points, by filter size: one launch holds 288
+# packed columns; the 2x2 entry points run wider layers as column blocks.  The head's oc stays within one launch.
+MAX_WIDTH = {2: 512, 3: 288}
+MAX_OC = 288
+# widest layer whose first convolution's weight gradient may go to the side stream (OVERLAP_WGRAD below)
+MAX_OVERLAP_WIDTH = 288
+
+
 def cs_of(c):
     """channel stride (floats) used for a c-channel grid tensor: multiple of 8."""
     return (c + 7) // 8 * 8
@@ -40,7 +48,7 @@ class Geometry:
         self.amax_n = int(_lib.load().mmlf_amax_entries(B, H, W))
         self.amax_head = int(_lib.load().mmlf_amax_head())             # tensor-maximum shards, then one entry per grid row
         self.amax_stride = int(_lib.load().mmlf_amax_shard_stride())
-        if self.alloc * 288 * 4 >= 2 ** 63 or self.NQ + 2 * self.P + 600 >= 2 ** 31:
+        if self.alloc * MAX_WIDTH[2] * 4 >= 2 ** 63 or self.NQ + 2 * self.P + 600 >= 2 ** 31:
             raise ValueError('batch x image too large for 32-bit grid positions')
 
     def buf(self, cs, device):
@@ -479,6 +487,9 @@ class Trunk:
         self.out_blocks.append(BlockSpec(f'out_net.{out_blocks - 1}', c, oc, None))
         if chs % 2 or cs_of(c) != c:
             raise ValueError('native trunk needs an even model_chs with 4*model_chs a multiple of 8')
+        if c > MAX_WIDTH[ksize] or oc > MAX_OC:
+            raise ValueError(f'native trunk: 4*model_chs = {c} (max {MAX_WIDTH[ksize]} with {ksize}x{ksize} filters), '
+                             f'{oc} output channels (max {MAX_OC})')
         # state_dict key -> element count of every parameter and BatchNorm buffer the blocks read through raw pointers
         # (check_params); h / v and i / d share their nets' keys
         self._numel = {}
@@ -893,7 +904,9 @@ class Trunk:
 
         while recs:
             rec = recs.pop()
-            wide = OVERLAP_WGRAD and rec.spec.cin >= 128 and self.ksize == 2
+            # (layers wider than one launch run their weight gradient as column blocks, the second of them on kernels the
+            # register budget of the overlap was not drawn up for: they stay on the main stream)
+            wide = OVERLAP_WGRAD and 128 <= rec.spec.cin <= MAX_OVERLAP_WIDTH and self.ksize == 2
             g, event, keep = self._block_bwd(geo, rec, p, grads, g, cs_g, 0, True, after_bn=settle, overlap=wide,
                                              packs=tape['packs'])
             settle()                        # (blocks without BatchNorm never called it)

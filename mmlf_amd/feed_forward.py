@@ -7,11 +7,13 @@ checkpoints load unchanged and the reference's train / validate drivers can use 
 On CUDA (= HIP on ROCm) tensors with four streams and model_ksize 2 or 3 the whole trunk runs in hand-written gfx950
 kernels through the C ABI (engine.Trunk; 3x3 filters on the exact-f32 kernels whatever MMLF_CONV_MODE says), with
 BatchNorm (the default) and, for model_ksize 2, also under model_no_batchnorm (ReLU-only blocks: both ReLUs in the
-convolutions' epilogues, no BatchNorm launch); there is no fallback on that path: a missing libmmlf_hip.so raises.
+convolutions' epilogues, no BatchNorm launch), for an even model_chs with 4 * model_chs a multiple of 8 and at most 512 with
+2x2 filters (layers wider than 288 channels run as column blocks) or 288 with 3x3 filters; there is no fallback
+on that path: a missing libmmlf_hip.so raises.
 That path is differentiable in the parameters and in the four view stacks, like the reference's nn.Conv2d tree; a net whose
 parameters are all frozen is differentiated in its inputs without any weight-gradient launch (_TrunkFn).
 CPU tensors, and the flags the README recipes never use (model_cross, other kernel sizes, model_no_batchnorm together
-with model_ksize 3, model_unet), run the module tree with stock torch ops ("plumbing path": BASELINE.json configs[0],
+with model_ksize 3, model_unet, wider nets), run the module tree with stock torch ops ("plumbing path": BASELINE.json configs[0],
 CPU tests, gloo rehearsal).
 """
 import numpy as np
@@ -235,7 +237,8 @@ class FeedForward(nn.Module):
         self.unet = bool(model_unet)
 
         self._native_ok = (not model_unet and model_ksize in (2, 3) and not model_cross and (bn or model_ksize == 2)
-                           and model_chs % 2 == 0 and (4 * model_chs) % 8 == 0 and 4 * model_chs <= 288 and oc <= 288)
+                           and model_chs % 2 == 0 and (4 * model_chs) % 8 == 0
+                           and 4 * model_chs <= (512 if model_ksize == 2 else 288) and oc <= 288)
         self._trunk = (Trunk(model_chs, model_in_blocks, model_out_blocks, model_views, oc,
                              model_batchnorm_momentum, ksize=model_ksize, batchnorm=bn) if self._native_ok else None)
         self._param_names = [n for n, _ in self.named_parameters()]
