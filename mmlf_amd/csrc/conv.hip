@@ -54,6 +54,23 @@ __device__ __forceinline__ void col_block_of(int n, int np_total, int &blk, int 
     blk = n >= npb ? 1 : 0;
     nl = n - blk * npb;
 }
+// What ONE column block of npb packed columns over nchunk chunks of 8 input channels takes in a packed filter, per layout.
+// The packing kernels place a block by these; the size queries, the launches and the audit read them through ConvPlan.
+//  exact f32: [chunk][tap(taps)][kh(2)][npb][4] floats
+__host__ __device__ static inline size_t packed_f32_block_floats(int taps, int nchunk, int npb)
+{
+    return (size_t)nchunk * taps * 2 * npb * 4;
+}
+//  split: [chunk][plane(planes)][tap(4)][npb][8] 16-bit values, planes = 3 (bf16) or 2 (f16) ...
+__host__ __device__ static inline size_t packed_split_planes_bytes(int planes, int nchunk, int npb)
+{
+    return (size_t)nchunk * planes * 4 * npb * 16;
+}
+//  ... and, behind the f16 planes, 1 / scale of every column of the block
+__host__ __device__ static inline size_t packed_split_block_bytes(int planes, int nchunk, int npb)
+{
+    return packed_split_planes_bytes(planes, nchunk, npb) + (planes == 2 ? (size_t)npb * 4 : 0);
+}
 
 // ---------------------------------------------------------------------------------------------
 // filter packing, exact f32: OIHW master (Cout, Cin, KS, KS) -> [chunk][tap(KS*KS)][kh][NP][4] with k = 8*chunk + 4*kh + s.
@@ -81,7 +98,7 @@ __global__ void pack_filter_f32_kernel(const float *__restrict__ w, float *__res
         if (ci < Cin && co < Cout) v = w[((size_t)co * Cin + ci) * TAPS + master_tap<KS>(tsrc, variant)];
         int blk, nl, npb;                  // (one block: the linear index idx)
         col_block_of(n, NP, blk, nl, npb);
-        out[(size_t)blk * nchunk * TAPS * 2 * npb * 4 + ((((size_t)c * TAPS + t) * 2 + kh) * npb + nl) * 4 + s] = v;
+        out[blk * packed_f32_block_floats(TAPS, nchunk, npb) + ((((size_t)c * TAPS + t) * 2 + kh) * npb + nl) * 4 + s] = v;
     }
 }
 
@@ -197,9 +214,9 @@ __device__ __forceinline__ void pack_filter_h2_column(const float *__restrict__ 
     const int tid = threadIdx.x;
     int blk, nl, npb;
     col_block_of(n, NP, blk, nl, npb);
-    char *const base = reinterpret_cast<char *>(packed) + (size_t)blk * ((size_t)nchunk * 8 * npb * 16 + (size_t)npb * 4);
+    char *const base = reinterpret_cast<char *>(packed) + blk * packed_split_block_bytes(2, nchunk, npb);
     unsigned short *const out = reinterpret_cast<unsigned short *>(base);
-    float *const unscale = reinterpret_cast<float *>(base + (size_t)nchunk * 8 * npb * 16);
+    float *const unscale = reinterpret_cast<float *>(base + packed_split_planes_bytes(2, nchunk, npb));
     const int K = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;
     auto at = [&](int k, int tap) -> size_t {      // OIHW index of (packed row k, column n, master tap)
         return dgrad ? ((size_t)k * Cin + n) * 4 + tap : ((size_t)n * Cin + k) * 4 + tap;
@@ -279,7 +296,7 @@ __global__ void pack_filter_split_kernel(const float *__restrict__ w, unsigned s
         split3(v, p[0], p[1], p[2]);
         int blk, nl, npb;
         col_block_of(n, NP, blk, nl, npb);
-        unsigned short *const ob = out + (size_t)blk * nchunk * 12 * npb * 8;
+        unsigned short *const ob = out + blk * packed_split_block_bytes(3, nchunk, npb) / 2;
         for (int pl = 0; pl < 3; ++pl) {
             ob[((((size_t)c * 3 + pl) * 4 + t) * npb + nl) * 8 + j] = (unsigned short)p[pl];
         }
@@ -1330,11 +1347,119 @@ static inline int f32_np(int ks, int N)
     const int nt = pick_nt(N);
     return nt > 0 ? nt * 32 : (ks == 2 ? wide_np(N) : -1);
 }
+// Packed column count NP of the split forward/dgrad kernels: 32, 80, then 16-column granularity up to
+// 128, then 288; above that the column blocks of wide_np.  Packing and launch pick by this one rule, so the layouts always agree.
+static inline int x6_np(int N)
+{
+    if (N > MMLF_MAX_N) return wide_np(N);
+    if (N <= 0) return -1;
+    if (N <= 32) return 32;
+    if (N <= 80) return 80;
+    if (N <= 128) return (N + 15) / 16 * 16;
+    return 288;
+}
+
+// The sixteen-wave variant (512-position tiles) serves the 80-column f16 kernels on pitches whose 513 + P position
+// window fits the 640-slot activation buffer (MMLF_CONV_NW16=0 turns it off).
+static bool conv_sixteen_waves(int planes, int np, const Grid &g)
+{
+    static const int on = [] { const char *e = getenv("MMLF_CONV_NW16"); return e ? atoi(e) : 1; }();
+    return on && planes == 2 && np == 80 && g.P + 513 <= 640;
+}
+// the register-streamed narrow kernel (conv4tap_rs_kernel) serves 80 packed columns over 4 or 9 input chunks (27 -> 70,
+// 70 -> 70) in the f16 split.
+// Where it runs (measured, profiles/r04_ab_bench_rs.log): on 96x96 training patches the two kernels take the same time
+// (0.94 ms per 70 -> 70 launch at bs=512 either way; whole step 1122-1127 patches/s both), so the tiled sixteen-wave
+// kernel keeps those launches; on pitches where that variant's 512 + P position window does not fit (full frames: the
+// 70 members of a 512x512 ESE scene) the tiled kernel falls back to eight waves and two window segments, and the
+// register-streamed kernel is 4.7 % faster end to end (0.436 vs 0.457 s per scene).  MMLF_CONV_RS=1 / 0 forces it on /
+// off for every eligible launch (A/B).
+static bool conv_rs_shape(int planes, int np, int nchunk, int nw)
+{
+    static const int mode = [] { const char *e = getenv("MMLF_CONV_RS"); return e ? atoi(e) : -1; }();
+    if (!(planes == 2 && np == 80 && (nchunk == 9 || nchunk == 4))) return false;
+    return mode < 0 ? nw == 8 : mode != 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The launch plan of a 2x2 convolution: everything about one launch of a layer that follows from (arithmetic path, input
+// channel stride, N, B, H, W) -- computed HERE and nowhere else.  The entry points copy it into ConvArgs and launch by it,
+// the size queries return its figures (mmlf_conv2x2_blocks: `blocks`, the rows of bn_partial; mmlf_packed_filter_*: the
+// bytes), and the bounds audit (mmlf_audit_conv_h2) derives every end from its fields, so what the audit certifies is the
+// launch itself.
+// How the fetched positions follow (positions are grid positions q; a buffer of channel stride cs holds alloc = NQpad + P +
+// 72 of them): the activation window of the LAST tile (first position NQpad - tile) is one contiguous window of tile + 1 + P
+// positions when that fits the 640 slots, else two 320-slot segments (rows y and y + 1) of 257 positions each, the second
+// one seg_delta + 320 further on; either way it ends at position NQpad + P.  The last piece of a window / segment fetches
+// a_tail positions only, the other lanes re-fetch the last of those.  The register-streamed kernel reads positions
+// Q0 + 32 w + 16 mb + r16 + {0, 1, P, P + 1} for every position of the padded grid: the same end.
+// A layer wider than 288 columns is ncb = 2 launches of this kind on column blocks (wide_np): the same tiles, windows and
+// workgroup count each, the packed filter's blocks back to back.
+// ---------------------------------------------------------------------------------------------
+constexpr int CONV_A_SLOTS = 640, CONV_SEG_SLOTS = 320;   // activation slots of conv4tap_x6s_kernel's LDS buffer; of a segment
+struct ConvPlan {
+    Grid g;
+    int np, ncb, npb, G;          // packed columns of the layer; column blocks (a launch each); columns, 16-column groups of one
+    int nw, tile;                 // waves per workgroup (8 or 16) and the positions of their tile
+    bool rs;                      // the register-streamed kernel runs the launch
+    int a_pieces, a_per_seg, a_tail, seg_slot, seg_delta;   // the tiled split kernels' activation window, as in ConvArgs
+    long long ntiles, ngroups;    // tiles, 32-position groups of the padded grid
+    int blocks;                   // workgroups of a launch (persistent: each walks tiles / groups b, b + blocks, ...)
+    size_t block_bytes;           // packed filter of one column block ...
+    long long unscale_off;        // ... and where behind its planes the columns' unscale factors start (f16 split; else -1)
+    long long last_in;            // last activation position a launch fetches (split paths)
+};
+// planes: 2 = f16 split, 3 = bf16 split, 0 = exact f32 (256-position tiles, one workgroup each; no window of this kind).
+// False: no such launch (what the entry points' argument checks refuse by name).
+static bool conv_plan(int planes, int cs_in, int N, int B, int H, int W, ConvPlan &p)
+{
+    p = {};
+    const Grid &g = p.g = make_grid(B, H, W);
+    p.np = planes ? x6_np(N) : f32_np(2, N);
+    if (p.np <= 0 || cs_in <= 0 || B <= 0 || H <= 0 || W <= 0) return false;
+    const int nchunk = cs_in / 8, cus = device_cus();
+    p.ncb = col_blocks(p.np); p.npb = p.np / p.ncb; p.G = p.npb / 16;
+    p.nw = conv_sixteen_waves(planes, p.npb, g) ? 16 : 8;
+    p.tile = 32 * p.nw;
+    p.ntiles = g.NQpad / p.tile; p.ngroups = g.NQpad / 32;
+    p.rs = conv_rs_shape(planes, p.npb, nchunk, p.nw);
+    if (!planes) {
+        p.blocks = (int)p.ntiles;
+        p.block_bytes = packed_f32_block_floats(4, nchunk, p.npb) * sizeof(float);
+        p.unscale_off = -1;
+        return true;
+    }
+    const int span = g.P + p.tile + 1;
+    if (span <= CONV_A_SLOTS) {   // one contiguous window of tile + 1 + P positions
+        p.a_pieces = p.a_per_seg = (span + 31) / 32; p.seg_slot = g.P; p.seg_delta = 0;
+    } else {                      // two segments: rows y and y+1, positions Q0 .. Q0 + 256 of each
+        p.a_per_seg = (MMLF_TILE + 1 + 31) / 32; p.a_pieces = 2 * p.a_per_seg; p.seg_slot = CONV_SEG_SLOTS; p.seg_delta = g.P - CONV_SEG_SLOTS;
+    }
+    p.a_tail = (p.seg_delta ? MMLF_TILE + 1 : span) - 32 * (p.a_per_seg - 1);
+    // persistent launches: one workgroup per CU (two for the narrow eight-wave variants); the register-streamed kernel's
+    // workgroups take eight groups at a time
+    const long long grid = p.rs ? cus : (p.G <= 6 && p.nw == 8 ? 2ll : 1ll) * cus, work = p.rs ? (p.ngroups + 7) / 8 : p.ntiles;
+    p.blocks = (int)(grid > work ? work : grid);
+    p.block_bytes = packed_split_block_bytes(planes, nchunk, p.npb);
+    p.unscale_off = planes == 2 ? (long long)packed_split_planes_bytes(planes, nchunk, p.npb) : -1;
+    const int seg = p.a_pieces / p.a_per_seg - 1;      // the segment of the window's last piece
+    p.last_in = p.rs ? g.NQpad - 1 + g.P + 1
+                     : (g.NQpad - p.tile) + seg * (CONV_SEG_SLOTS + p.seg_delta) + 32 * (p.a_per_seg - 1) + p.a_tail - 1;
+    return true;
+}
+// (the byte figures do not depend on the frame)
+static int64_t packed_filter_bytes(int planes, int K, int N)
+{
+    ConvPlan p;
+    if (K <= 0 || !conv_plan(planes, (K + 7) / 8 * 8, N, 1, 1, 1, p)) return -1;
+    return (int64_t)p.ncb * p.block_bytes;
+}
 static int64_t packed_filter_f32_floats(int ks, int K, int N)
 {
-    const int np = f32_np(ks, N);
+    if (ks == 2) return packed_filter_bytes(0, K, N) < 0 ? -1 : packed_filter_bytes(0, K, N) / 4;
+    const int np = f32_np(ks, N);      // (3x3: ONE launch walks its column blocks, conv9_shape)
     if (np < 0 || K <= 0) return -1;
-    return (int64_t)((K + 7) / 8) * ks * ks * 2 * np * 4;
+    return (int64_t)packed_f32_block_floats(ks * ks, (K + 7) / 8, np);
 }
 
 static int pack_filter_f32(const char *who, int ks, const float *w, float *packed, int Cout, int Cin, int variant,
@@ -1347,7 +1472,7 @@ static int pack_filter_f32(const char *who, int ks, const float *w, float *packe
     const int NP = f32_np(ks, N);
     MMLF_CHECK_ARG(NP > 0, "%s: N=%d not supported (max %d)", who, N, ks == 2 ? MMLF_MAX_N_WIDE : MMLF_MAX_N);
     const int nchunk = (K + 7) / 8;
-    const long long total = (long long)nchunk * ks * ks * 2 * NP * 4;
+    const long long total = (long long)packed_f32_block_floats(ks * ks, nchunk, NP);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(ks == 2 ? pack_filter_f32_kernel<2> : pack_filter_f32_kernel<3>, dim3(blocks), dim3(256), 0,
@@ -1378,8 +1503,8 @@ static void conv_buffer_bytes(ConvArgs &a, const Grid &g, long long alloc)
 
 // The argument checks and the ConvArgs fields that every forward / data-gradient entry point shares.  who = the entry
 // point as the caller named it, ks = filter size (window slack: taps reach (ks-1)(P+1) past a tile), np = packed columns
-// by the path's own rule (<= 0: N not supported).
-static int conv_common_args(const char *who, int ks, int np, ConvArgs &a, Grid &g, const float *in, int cs_in, int K,
+// by the path's own rule (<= 0: N not supported), g = make_grid(B, H, W).
+static int conv_common_args(const char *who, int ks, int np, ConvArgs &a, const Grid &g, const float *in, int cs_in, int K,
                             const void *packed, const float *bias, int N, float *out, int cs_out, int N_store,
                             int out_shift, int vh, int vw, int B, int H, int W, int relu, const float *relu_ref, int cs_ref)
 {
@@ -1390,7 +1515,6 @@ static int conv_common_args(const char *who, int ks, int np, ConvArgs &a, Grid &
     MMLF_CHECK_ARG(np > 0, "%s: N=%d not supported (max %d)", who, N, ks == 2 ? MMLF_MAX_N_WIDE : MMLF_MAX_N);
     MMLF_CHECK_ARG(N_store > 0 && N_store <= cs_out && N_store <= np, "%s: N_store=%d vs cs_out=%d NP=%d", who,
                    N_store, cs_out, np);
-    g = make_grid(B, H, W);
     MMLF_CHECK_ARG(out_shift >= 0 && out_shift <= g.P + 1, "%s: out_shift=%d", who, out_shift);
     MMLF_CHECK_ARG(!relu_ref || cs_ref >= N_store, "%s: cs_ref=%d < N_store", who, cs_ref);
     MMLF_CHECK_ARG(g.NQpad + (ks - 1) * g.P + 64 < (1ll << 31), "%s: batch x image too large for 32-bit grid positions", who);
@@ -1403,19 +1527,19 @@ static int conv_common_args(const char *who, int ks, int np, ConvArgs &a, Grid &
     return 0;
 }
 
-// Column block b of a wide 2x2 layer (wide_np): the launch arguments of the whole layer `a`, narrowed to the block's npb
-// packed columns.  packed_block_bytes: what one block's packed filter takes; unscale_off: where its columns' unscale factors
-// start in it (f16 split) or -1.  False: the block stores nothing (a channel slice that ends in front of it).
-static bool conv_block_args(const ConvArgs &a, int b, int npb, size_t packed_block_bytes, long long unscale_off, ConvArgs &ab)
+// Column block b of a 2x2 layer (the only one, or one of a wide layer's: wide_np): the launch arguments of the whole layer
+// `a`, narrowed to the block's p.npb packed columns and its part of the packed filter.  False: the block stores nothing (a
+// channel slice that ends in front of it).
+static bool conv_block_args(const ConvArgs &a, const ConvPlan &p, int b, ConvArgs &ab)
 {
     ab = a;
-    const int c0 = b * npb;
+    const int c0 = b * p.npb, npb = p.npb;
     if (a.n_store <= c0) return false;
     ab.n_store = a.n_store - c0 < npb ? a.n_store - c0 : npb;
     ab.n_true = a.n_true - c0 < npb ? a.n_true - c0 : npb;
-    const char *wp = reinterpret_cast<const char *>(a.wp) + (size_t)b * packed_block_bytes;
+    const char *wp = reinterpret_cast<const char *>(a.wp) + (size_t)b * p.block_bytes;
     ab.wp = reinterpret_cast<const float *>(wp);
-    ab.w_unscale = unscale_off >= 0 ? reinterpret_cast<const float *>(wp + unscale_off) : nullptr;
+    ab.w_unscale = p.unscale_off >= 0 ? reinterpret_cast<const float *>(wp + p.unscale_off) : nullptr;
     if (a.bias) ab.bias = a.bias + c0;
     ab.out = a.out + c0;
     ab.out_bytes = a.out_bytes - 4ll * c0;
@@ -1449,27 +1573,26 @@ extern "C" int mmlf_conv2x2(const float *in, int cs_in, int K, const float *pack
                             float *out, int cs_out, int N_store, int out_shift, int vh, int vw, int B, int H,
                             int W, int relu, const float *relu_ref, int cs_ref, void *stream)
 {
-    const int np = f32_np(2, N);
+    ConvPlan p;
+    const bool planned = conv_plan(0, cs_in, N, B, H, W, p);
     ConvArgs a;
-    Grid g;
-    if (conv_common_args("mmlf_conv2x2", 2, np, a, g, in, cs_in, K, packed, bias, N, out, cs_out, N_store, out_shift, vh,
+    if (conv_common_args("mmlf_conv2x2", 2, p.np, a, p.g, in, cs_in, K, packed, bias, N, out, cs_out, N_store, out_shift, vh,
                          vw, B, H, W, relu, relu_ref, cs_ref))
         return 1;
-    const long long ntiles = g.NQpad / MMLF_TILE;
+    MMLF_CHECK_ARG(planned, "mmlf_conv2x2: no launch plan");      // (the checks above refuse what conv_plan refuses)
     hipStream_t st = (hipStream_t)stream;
-    const int ncb = col_blocks(np), npb = np / ncb;
-    for (int b = 0; b < ncb; ++b) {
-        ConvArgs ab = a;
-        if (ncb > 1 && !conv_block_args(a, b, npb, (size_t)a.nchunk * 4 * 2 * npb * 4 * sizeof(float), -1, ab)) continue;
+    for (int b = 0; b < p.ncb; ++b) {
+        ConvArgs ab;
+        if (!conv_block_args(a, p, b, ab)) continue;
         int rc;
-        switch (npb / 32) {
-        case 1: rc = launch_conv_f32<2, 1>(ab, ntiles, 1, st); break;
-        case 3: rc = launch_conv_f32<2, 3>(ab, ntiles, 1, st); break;
-        case 4: rc = launch_conv_f32<2, 4>(ab, ntiles, 1, st); break;
-        case 5: rc = launch_conv_f32<2, 5>(ab, ntiles, 1, st); break;
-        case 6: rc = launch_conv_f32<2, 6>(ab, ntiles, 1, st); break;
-        case 8: rc = launch_conv_f32<2, 8>(ab, ntiles, 1, st); break;
-        default: rc = launch_conv_f32<2, 9>(ab, ntiles, 1, st); break;
+        switch (p.npb / 32) {
+        case 1: rc = launch_conv_f32<2, 1>(ab, p.blocks, 1, st); break;
+        case 3: rc = launch_conv_f32<2, 3>(ab, p.blocks, 1, st); break;
+        case 4: rc = launch_conv_f32<2, 4>(ab, p.blocks, 1, st); break;
+        case 5: rc = launch_conv_f32<2, 5>(ab, p.blocks, 1, st); break;
+        case 6: rc = launch_conv_f32<2, 6>(ab, p.blocks, 1, st); break;
+        case 8: rc = launch_conv_f32<2, 8>(ab, p.blocks, 1, st); break;
+        default: rc = launch_conv_f32<2, 9>(ab, p.blocks, 1, st); break;
         }
         if (rc) return rc;
     }
@@ -1477,24 +1600,7 @@ extern "C" int mmlf_conv2x2(const float *in, int cs_in, int K, const float *pack
 }
 
 // ------------------------------------------------------------------ split-bf16 ("bf16x6") entry points
-// Packed column count NP of the split forward/dgrad kernels: 32, 80, then 16-column granularity up to
-// 128, then 288; above that the column blocks of wide_np.  Packing and launch pick by this one rule, so the layouts always agree.
-static inline int x6_np(int N)
-{
-    if (N > MMLF_MAX_N) return wide_np(N);
-    if (N <= 0) return -1;
-    if (N <= 32) return 32;
-    if (N <= 80) return 80;
-    if (N <= 128) return (N + 15) / 16 * 16;
-    return 288;
-}
-
-extern "C" int64_t mmlf_packed_filter_split_bytes(int K, int N)
-{
-    const int np = x6_np(N);
-    if (np < 0 || K <= 0) return -1;
-    return (int64_t)((K + 7) / 8) * 12 * np * 16;
-}
+extern "C" int64_t mmlf_packed_filter_split_bytes(int K, int N) { return packed_filter_bytes(3, K, N); }
 
 extern "C" int mmlf_pack_filter_split(const float *w, void *packed, int Cout, int Cin, int variant, int dgrad,
                                       void *stream)
@@ -1513,20 +1619,6 @@ extern "C" int mmlf_pack_filter_split(const float *w, void *packed, int Cout, in
     return mmlf_launch_status("mmlf_pack_filter_split");
 }
 
-// persistent launches: one workgroup per CU (two for the narrow eight-wave variants), each walks tiles b, b+grid, ...
-static long long conv_split_blocks(int G, long long ntiles, int nw = 8)
-{
-    const long long grid = (G <= 6 && nw == 8 ? 2ll : 1ll) * device_cus();
-    return grid > ntiles ? ntiles : grid;
-}
-// The sixteen-wave variant (512-position tiles) serves the 80-column f16 kernels on pitches whose 513 + P position
-// window fits the 640-slot activation buffer (MMLF_CONV_NW16=0 turns it off).
-static bool conv_sixteen_waves(int planes, int np, const Grid &g)
-{
-    static const int on = [] { const char *e = getenv("MMLF_CONV_NW16"); return e ? atoi(e) : 1; }();
-    return on && planes == 2 && np == 80 && g.P + 513 <= 640;
-}
-
 // The transposed epilogue (conv_epilogue16_tr) serves the launch kinds plain / ReLU / ReLU + mask-out / mask-in when the
 // output rows can take 16-byte stores.  MMLF_CONV_TR=0 turns it off for the whole process (A/B; the ReLU mask words then
 // have the other layout, for their producer and their consumer alike).
@@ -1540,8 +1632,45 @@ static bool conv_tr_fits(const ConvArgs &a)
     return a.n_store % 4 == 0 && a.cs_out % 4 == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
 }
 
-template <int G, int PL, int EPI, bool TR = false>
-static int launch_conv_x6s_epi(const ConvArgs &a, long long ntiles, hipStream_t st)
+// ---- launch kind -> epilogue build
+// The launch kinds of a training step get an epilogue build of their own on the hot shapes (f16 split: the 70- and 280-wide
+// layers, the column blocks of the wider ones); every other combination of options runs the generic one, whose mask words
+// have conv_epilogue16's layout for producer and consumer alike.  A kernel family says which kinds it has builds of, in
+// which orientation, and conv_launch_epi picks by that -- the one place that does.
+struct EpiBuilds {
+    unsigned std, tr;        // bit k: launch kind k (the EPI_* bits of a launch's options) has a build in the standard / transposed form
+    // the plain kind runs its transposed build.  Not on the 80-column kernels, where it measured 3 % slower
+    // (profiles/r05_kbench_tr.log; their transposed plain builds are compiled and never launched)
+    bool tr_plain;
+    // transposed on one-segment activation windows only: with two segments (full frames, pitch > 383) the 288-column tiled
+    // kernel's ReLU launches measured 26.7 ms against 24.3 in the other orientation, profiles/r05_ese_tr_kernel_stats.log,
+    // while at training pitches they are 0.5-2 % faster.  The condition depends on (B, H, W) and the kernel alone, so a
+    // mask's producer and its consumer always agree.
+    bool tr_one_segment;
+    // Column blocks of a wide layer: ReLU mask words in the transposed form ONLY -- its 2 x 2 words per lane let the two
+    // blocks share a tile's 4096 words, conv_epilogue16's eight words per lane do not.  (The blocks' plain and ReLU kinds
+    // are built in the transposed form alone: a launch that cannot take 16-byte stores runs the generic build, which
+    // spills at G = 16.)
+    bool masks_tr_only;
+};
+constexpr unsigned epi_bit(int kind) { return 1u << kind; }
+constexpr unsigned EPI_TR_KINDS = epi_bit(EPI_PLAIN) | epi_bit(EPI_RELU) | epi_bit(EPI_RELU | EPI_MASK_OUT) | epi_bit(EPI_BITS_IN);
+constexpr EpiBuilds EPI_BUILDS_RS = {EPI_TR_KINDS | epi_bit(EPI_STATS), EPI_TR_KINDS, false, false, false};       // register-streamed
+constexpr EpiBuilds EPI_BUILDS_G5 = {EPI_TR_KINDS | epi_bit(EPI_STATS) | epi_bit(EPI_REF_IN), EPI_TR_KINDS, false, false, false};
+constexpr EpiBuilds EPI_BUILDS_G18 = {EPI_TR_KINDS | epi_bit(EPI_STATS) | epi_bit(EPI_REF_IN), EPI_TR_KINDS, true, true, false};
+constexpr EpiBuilds EPI_BUILDS_WIDE = {epi_bit(EPI_STATS) | epi_bit(EPI_REF_IN), EPI_TR_KINDS, true, false, true};   // G = 10, 12, 16
+constexpr EpiBuilds EPI_BUILDS_NONE = {0, 0, false, false, false};                                                    // generic only
+
+// the tiled kernels (conv4tap_x6s_kernel) of G 16-column groups and PL operand planes
+template <int G, int PL>
+struct ConvTiledKernels {
+    static constexpr EpiBuilds builds = PL != 2 ? EPI_BUILDS_NONE : G == 5 ? EPI_BUILDS_G5 : G == 18 ? EPI_BUILDS_G18
+                                        : (G == 10 || G == 12 || G == 16) ? EPI_BUILDS_WIDE : EPI_BUILDS_NONE;
+    template <int EPI, bool TR> static int launch(const ConvArgs &a, const ConvPlan &p, hipStream_t st);
+};
+template <int G, int PL>
+template <int EPI, bool TR>
+int ConvTiledKernels<G, PL>::launch(const ConvArgs &a, const ConvPlan &p, hipStream_t st)
 {
     constexpr size_t lds_pipe = 2 * (2 * 640 + 4 * PL * G * 16) * sizeof(float4);
     constexpr size_t lds_stats = 8 * (G * 16) * 2 * sizeof(double);
@@ -1559,137 +1688,92 @@ static int launch_conv_x6s_epi(const ConvArgs &a, long long ntiles, hipStream_t 
                                                            lds_pipe16 + (TR ? lds_coef : lds_stats16), "mmlf_conv2x2_h2(16 waves)"); }))
                 return 1;
             const size_t lds16 = lds_pipe16 + (TR ? lds_coef : a.bn_partial ? lds_stats16 : 0);
-            const long long grid16 = conv_split_blocks(G, ntiles, 16);
-            hipLaunchKernelGGL((conv4tap_x6s_kernel<G, PL, EPI, 16, TR>), dim3((unsigned)grid16), dim3(1024), lds16, st, a, (int)ntiles);
+            hipLaunchKernelGGL((conv4tap_x6s_kernel<G, PL, EPI, 16, TR>), dim3((unsigned)p.blocks), dim3(1024), lds16, st, a, (int)p.ntiles);
             return mmlf_launch_status("mmlf_conv2x2_h2(16 waves)");
         }
     }
     const size_t lds = lds_pipe + (TR ? lds_coef : a.bn_partial ? lds_stats : 0);
-    const long long grid = conv_split_blocks(G, ntiles);
-    hipLaunchKernelGGL((conv4tap_x6s_kernel<G, PL, EPI, 8, TR>), dim3((unsigned)grid), dim3(512), lds, st, a, (int)ntiles);
+    hipLaunchKernelGGL((conv4tap_x6s_kernel<G, PL, EPI, 8, TR>), dim3((unsigned)p.blocks), dim3(512), lds, st, a, (int)p.ntiles);
     return mmlf_launch_status(PL == 3 ? "mmlf_conv2x2_split" : "mmlf_conv2x2_h2");
 }
 
-// the register-streamed narrow kernel (conv4tap_rs_kernel) serves 80 packed columns over 4 or 9 input chunks (27 -> 70,
-// 70 -> 70) in the f16 split.
-// Where it runs (measured, profiles/r04_ab_bench_rs.log): on 96x96 training patches the two kernels take the same time
-// (0.94 ms per 70 -> 70 launch at bs=512 either way; whole step 1122-1127 patches/s both), so the tiled sixteen-wave
-// kernel keeps those launches; on pitches where that variant's 512 + P position window does not fit (full frames: the
-// 70 members of a 512x512 ESE scene) the tiled kernel falls back to eight waves and two window segments, and the
-// register-streamed kernel is 4.7 % faster end to end (0.436 vs 0.457 s per scene).  MMLF_CONV_RS=1 / 0 forces it on /
-// off for every eligible launch (A/B).
-static int conv_rs_mode()
-{
-    static const int mode = [] { const char *e = getenv("MMLF_CONV_RS"); return e ? atoi(e) : -1; }();
-    return mode;
-}
-static bool conv_rs_shape(int planes, int np, int nchunk, int nw)
-{
-    if (!(planes == 2 && np == 80 && (nchunk == 9 || nchunk == 4))) return false;
-    const int mode = conv_rs_mode();
-    return mode < 0 ? nw == 8 : mode != 0;
-}
-static long long conv_rs_blocks(long long ngroups)
-{
-    const long long grid = device_cus(), need = (ngroups + 7) / 8;
-    return grid > need ? need : grid;
-}
-template <int G, int NCH, int EPI, bool TR = false>
-static int launch_conv_rs_epi(const ConvArgs &a, long long ngroups, hipStream_t st)
+// the register-streamed kernels (conv4tap_rs_kernel; where they run: conv_rs_shape) over NCH input chunks
+template <int G, int NCH>
+struct ConvRsKernels {
+    static constexpr EpiBuilds builds = EPI_BUILDS_RS;
+    template <int EPI, bool TR> static int launch(const ConvArgs &a, const ConvPlan &p, hipStream_t st);
+};
+template <int G, int NCH>
+template <int EPI, bool TR>
+int ConvRsKernels<G, NCH>::launch(const ConvArgs &a, const ConvPlan &p, hipStream_t st)
 {
     constexpr size_t lds = (size_t)NCH * 2 * 4 * (G * 16) * 16 + (TR ? 2 * (G * 16) * sizeof(float) : 8 * (G * 16) * 2 * sizeof(double));
     static PerDeviceOnce attr_once;
     if (attr_once.run([] { return mmlf_allow_lds(reinterpret_cast<const void *>(conv4tap_rs_kernel<G, NCH, EPI, TR>), lds, "mmlf_conv2x2_h2(register-streamed)"); }))
         return 1;
-    hipLaunchKernelGGL((conv4tap_rs_kernel<G, NCH, EPI, TR>), dim3((unsigned)conv_rs_blocks(ngroups)), dim3(512), lds, st, a, (int)ngroups);
+    hipLaunchKernelGGL((conv4tap_rs_kernel<G, NCH, EPI, TR>), dim3((unsigned)p.blocks), dim3(512), lds, st, a, (int)p.ngroups);
     return mmlf_launch_status("mmlf_conv2x2_h2(register-streamed)");
 }
-// launch kind -> epilogue build.  tr: the transposed form, for the kinds that have one
-// (TR_PLAIN: whether the plain kind has one too -- on the 80-column kernels it measured 3 % slower: profiles/r05_kbench_tr.log;
-//  TR_SHAPE: a condition on the launch geometry -- the 288-column tiled kernel takes the transposed form on small pitches only:
-//  with two-segment activation windows (full frames, pitch > 383) its ReLU launches measured 26.7 ms against 24.3 in the other
-//  orientation, profiles/r05_ese_tr_kernel_stats.log, while at training pitches they are 0.5-2 % faster.  The condition depends
-//  on (B, H, W) and the kernel alone, so a mask's producer and its consumer always agree.)
-#define MMLF_CONV_KIND_SWITCH(LAUNCH, TR_PLAIN, TR_SHAPE, ...)                                                                              \
-    do {                                                                                                                \
-        const int kind = (a.relu ? EPI_RELU : 0) | (a.bn_partial ? EPI_STATS : 0) | (a.relu_mask_in ? EPI_BITS_IN : 0) | \
-                         (a.ref ? EPI_REF_IN : 0) | (a.relu_mask_out ? EPI_MASK_OUT : 0);                               \
-        const bool tr = conv_tr_enabled() && (TR_SHAPE) && conv_tr_fits(a);                                             \
-        if ((a.relu_mask_in || a.relu_mask_out) && conv_tr_enabled() && (TR_SHAPE) && !tr)                              \
-            return mmlf_fail("mmlf_conv2x2_h2: ReLU mask words need n_store %% 4 == 0 and a 16-byte aligned output");   \
-        switch (kind) {                                                                                                 \
-        case EPI_PLAIN: return tr && TR_PLAIN ? LAUNCH<__VA_ARGS__, EPI_PLAIN, true>(a, n, st) : LAUNCH<__VA_ARGS__, EPI_PLAIN>(a, n, st); \
-        case EPI_RELU: return tr ? LAUNCH<__VA_ARGS__, EPI_RELU, true>(a, n, st) : LAUNCH<__VA_ARGS__, EPI_RELU>(a, n, st); \
-        case EPI_RELU | EPI_MASK_OUT:                                                                                   \
-            return tr ? LAUNCH<__VA_ARGS__, EPI_RELU | EPI_MASK_OUT, true>(a, n, st) : LAUNCH<__VA_ARGS__, EPI_RELU | EPI_MASK_OUT>(a, n, st); \
-        case EPI_BITS_IN: return tr ? LAUNCH<__VA_ARGS__, EPI_BITS_IN, true>(a, n, st) : LAUNCH<__VA_ARGS__, EPI_BITS_IN>(a, n, st); \
-        case EPI_STATS: return LAUNCH<__VA_ARGS__, EPI_STATS>(a, n, st);                                                \
-        default: break;                                                                                                 \
-        }                                                                                                               \
-    } while (0)
-template <int G, int NCH>
-static int launch_conv_rs(const ConvArgs &a, long long n, hipStream_t st)
-{
-    MMLF_CONV_KIND_SWITCH(launch_conv_rs_epi, false, true, G, NCH);
-    return launch_conv_rs_epi<G, NCH, EPI_GENERIC>(a, n, st);
-}
 
-// the launch kinds of a training step get their own epilogue build on the hot shapes (f16 split, 70- and 280-wide
-// layers); every other combination of options runs the generic one
-template <int G, int PL>
-static int launch_conv_x6s(const ConvArgs &a, long long ntiles, hipStream_t st)
+// kernel family K (its `builds`), launch options of `a` -> the epilogue build that runs
+template <class K, int KIND>
+static bool conv_launch_kind(int kind, bool tr, const ConvArgs &a, const ConvPlan &p, hipStream_t st, int &rc)
 {
-    if constexpr (PL == 2 && G == 5) {
-        if (conv_rs_shape(PL, G * 16, a.nchunk, a.nw)) {
-            const long long ngroups = ntiles * a.nw;            // 32-position groups of the padded grid
-            return a.nchunk == 9 ? launch_conv_rs<G, 9>(a, ngroups, st) : launch_conv_rs<G, 4>(a, ngroups, st);
-        }
+    constexpr EpiBuilds F = K::builds;
+    if (kind != KIND) return false;
+    if constexpr ((F.tr & epi_bit(KIND)) != 0) {
+        if (tr && (KIND != EPI_PLAIN || F.tr_plain)) { rc = K::template launch<KIND, true>(a, p, st); return true; }
     }
-    if constexpr (PL == 2 && (G == 5 || G == 18)) {
-        const long long n = ntiles;
-        if (a.ref && !a.relu && !a.bn_partial && !a.relu_mask_in && !a.relu_mask_out)
-            return launch_conv_x6s_epi<G, PL, EPI_REF_IN>(a, n, st);
-        MMLF_CONV_KIND_SWITCH(launch_conv_x6s_epi, G == 18, G != 18 || a.seg_delta == 0, G, PL);
-    }
-    if constexpr (PL == 2 && (G == 10 || G == 12 || G == 16)) {
-        // Column blocks of a wide layer: the launch kinds of a training step get their own builds, as on the 280-wide layer (the
-        // generic G = 16 build spills).  The transposed form at every pitch, and ReLU mask words in that form ONLY: its 2 x 2
-        // words per lane let the two blocks share a tile's 4096 words, conv_epilogue16's eight words per lane do not.
-        const long long n = ntiles;
+    if constexpr ((F.std & epi_bit(KIND)) != 0) { rc = K::template launch<KIND, false>(a, p, st); return true; }
+    return false;            // (a kind without a build in the orientation the launch takes: the generic one)
+}
+template <class K>
+static int conv_launch_epi(const ConvArgs &a, const ConvPlan &p, hipStream_t st)
+{
+    constexpr EpiBuilds F = K::builds;
+    if constexpr ((F.std | F.tr) != 0) {
         const int kind = (a.relu ? EPI_RELU : 0) | (a.bn_partial ? EPI_STATS : 0) | (a.relu_mask_in ? EPI_BITS_IN : 0) |
                          (a.ref ? EPI_REF_IN : 0) | (a.relu_mask_out ? EPI_MASK_OUT : 0);
-        const bool tr = conv_tr_enabled() && conv_tr_fits(a);
-        if ((a.relu_mask_in || a.relu_mask_out) && !tr)
+        const bool masks = a.relu_mask_in || a.relu_mask_out, shape = !F.tr_one_segment || a.seg_delta == 0;
+        const bool tr = conv_tr_enabled() && shape && conv_tr_fits(a);      // the transposed form, for the kinds that have one
+        if (masks && !tr && F.masks_tr_only)
             return mmlf_fail("mmlf_conv2x2_h2: N > %d keeps ReLU mask words in the transposed layout only (n_store %% 4 == 0, a "
                              "16-byte aligned output, MMLF_CONV_TR not 0)", MMLF_MAX_N);
-        switch (kind) {
-        case EPI_PLAIN: if (tr) return launch_conv_x6s_epi<G, PL, EPI_PLAIN, true>(a, n, st); break;
-        case EPI_RELU: if (tr) return launch_conv_x6s_epi<G, PL, EPI_RELU, true>(a, n, st); break;
-        case EPI_RELU | EPI_MASK_OUT: return launch_conv_x6s_epi<G, PL, EPI_RELU | EPI_MASK_OUT, true>(a, n, st);
-        case EPI_BITS_IN: return launch_conv_x6s_epi<G, PL, EPI_BITS_IN, true>(a, n, st);
-        case EPI_STATS: return launch_conv_x6s_epi<G, PL, EPI_STATS>(a, n, st);
-        case EPI_REF_IN: return launch_conv_x6s_epi<G, PL, EPI_REF_IN>(a, n, st);
-        default: break;
-        }
-        if (a.relu_mask_in || a.relu_mask_out) return mmlf_fail("mmlf_conv2x2_h2: N > %d: this combination of ReLU mask options has no build", MMLF_MAX_N);
+        if (masks && !tr && conv_tr_enabled() && shape)
+            return mmlf_fail("mmlf_conv2x2_h2: ReLU mask words need n_store %% 4 == 0 and a 16-byte aligned output");
+        int rc = 0;
+        if (conv_launch_kind<K, EPI_PLAIN>(kind, tr, a, p, st, rc) || conv_launch_kind<K, EPI_RELU>(kind, tr, a, p, st, rc) ||
+            conv_launch_kind<K, EPI_RELU | EPI_MASK_OUT>(kind, tr, a, p, st, rc) || conv_launch_kind<K, EPI_BITS_IN>(kind, tr, a, p, st, rc) ||
+            conv_launch_kind<K, EPI_STATS>(kind, tr, a, p, st, rc) || conv_launch_kind<K, EPI_REF_IN>(kind, tr, a, p, st, rc))
+            return rc;
+        if (masks && F.masks_tr_only)
+            return mmlf_fail("mmlf_conv2x2_h2: N > %d: this combination of ReLU mask options has no build", MMLF_MAX_N);
     }
-    // (other widths: the generic build, whose mask words have conv_epilogue16's layout for producer and consumer alike)
-    return launch_conv_x6s_epi<G, PL, EPI_GENERIC>(a, ntiles, st);
+    return K::template launch<EPI_GENERIC, false>(a, p, st);
+}
+
+template <int G, int PL>
+static int launch_conv_x6s(const ConvArgs &a, const ConvPlan &p, hipStream_t st)
+{
+    if constexpr (PL == 2 && G == 5) {
+        if (p.rs) return a.nchunk == 9 ? conv_launch_epi<ConvRsKernels<G, 9>>(a, p, st) : conv_launch_epi<ConvRsKernels<G, 4>>(a, p, st);
+    }
+    return conv_launch_epi<ConvTiledKernels<G, PL>>(a, p, st);
 }
 
 template <int PL>
-static int launch_conv_split(int np, const ConvArgs &a, long long ntiles, hipStream_t st)
+static int launch_conv_split(const ConvArgs &a, const ConvPlan &p, hipStream_t st)
 {
-    switch (np) {
-    case 32: return launch_conv_x6s<2, PL>(a, ntiles, st);
-    case 80: return launch_conv_x6s<5, PL>(a, ntiles, st);
-    case 96: return launch_conv_x6s<6, PL>(a, ntiles, st);
-    case 112: return launch_conv_x6s<7, PL>(a, ntiles, st);
-    case 128: return launch_conv_x6s<8, PL>(a, ntiles, st);
-    case 160: return launch_conv_x6s<10, PL>(a, ntiles, st);      // (160, 192, 256: column blocks of a wide layer)
-    case 192: return launch_conv_x6s<12, PL>(a, ntiles, st);
-    case 256: return launch_conv_x6s<16, PL>(a, ntiles, st);
-    default: return launch_conv_x6s<18, PL>(a, ntiles, st);
+    switch (p.npb) {
+    case 32: return launch_conv_x6s<2, PL>(a, p, st);
+    case 80: return launch_conv_x6s<5, PL>(a, p, st);
+    case 96: return launch_conv_x6s<6, PL>(a, p, st);
+    case 112: return launch_conv_x6s<7, PL>(a, p, st);
+    case 128: return launch_conv_x6s<8, PL>(a, p, st);
+    case 160: return launch_conv_x6s<10, PL>(a, p, st);      // (160, 192, 256: column blocks of a wide layer)
+    case 192: return launch_conv_x6s<12, PL>(a, p, st);
+    case 256: return launch_conv_x6s<16, PL>(a, p, st);
+    default: return launch_conv_x6s<18, PL>(a, p, st);
     }
 }
 
@@ -1699,37 +1783,26 @@ static int conv_split_impl(const char *who, int planes, const float *in, int cs_
                            const float *in_amax, float *out_amax, double *bn_partial, void *stream,
                            unsigned *relu_mask_out = nullptr, const unsigned *relu_mask_in = nullptr)
 {
-    const int np = x6_np(N);
+    ConvPlan p;
+    const bool planned = conv_plan(planes, cs_in, N, B, H, W, p);
     ConvArgs a;
-    Grid g;
-    if (conv_common_args(who, 2, np, a, g, in, cs_in, K, packed, bias, N, out, cs_out, N_store, out_shift, vh, vw, B, H, W, relu,
+    if (conv_common_args(who, 2, p.np, a, p.g, in, cs_in, K, packed, bias, N, out, cs_out, N_store, out_shift, vh, vw, B, H, W, relu,
                          relu_ref, cs_ref))
         return 1;
+    MMLF_CHECK_ARG(planned, "%s: no launch plan", who);           // (the checks above refuse what conv_plan refuses)
     MMLF_CHECK_ARG(!(relu_ref && relu_mask_in), "%s: relu_ref and relu_mask_in are alternatives", who);
     MMLF_CHECK_ARG((long long)cs_in * 4 * 64 < (1ll << 31), "%s: cs_in too large", who);
     MMLF_CHECK_ARG(planes == 3 || in_amax, "%s: the f16 split needs the input's max |x|", who);
     MMLF_CHECK_ARG(!bn_partial || (planes == 2 && N_store >= N), "%s: BatchNorm statistics need the f16 split path", who);
     a.in_amax = in_amax; a.out_amax = out_amax; a.bn_partial = bn_partial; a.bn_stride = N;
     a.relu_mask_out = relu_mask_out; a.relu_mask_in = relu_mask_in;
-    const int ncb = col_blocks(np), npb = np / ncb;
-    // the f16-packed filter (of a column block) ends with its columns' unscale factors
-    const size_t plane_bytes = (size_t)(cs_in / 8) * (planes == 2 ? 8 : 12) * npb * 16;
-    a.w_unscale = planes == 2 ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(packed) + plane_bytes) : nullptr;
-    a.nw = conv_sixteen_waves(planes, np, g) ? 16 : 8;
-    const int tile = 32 * a.nw;
-    if (g.P + tile + 1 <= 640) {   // one contiguous window of tile + 1 + P positions
-        a.a_pieces = a.a_per_seg = (g.P + tile + 1 + 31) / 32; a.seg_slot = g.P; a.seg_delta = 0;
-    } else {                  // two 320-slot segments: rows y and y+1, positions Q0 .. Q0 + 256 of each
-        a.a_per_seg = 9; a.a_pieces = 18; a.seg_slot = 320; a.seg_delta = g.P - 320;
-    }
-    a.a_tail = (a.seg_delta ? 257 : g.P + tile + 1) - 32 * (a.a_per_seg - 1);
-    const long long ntiles = g.NQpad / tile;
+    a.nw = p.nw;
+    a.a_pieces = p.a_pieces; a.a_per_seg = p.a_per_seg; a.a_tail = p.a_tail; a.seg_slot = p.seg_slot; a.seg_delta = p.seg_delta;
     hipStream_t st = (hipStream_t)stream;
-    for (int b = 0; b < ncb; ++b) {      // one launch; a wide layer: one per column block, same tiles and workgroups
-        ConvArgs ab = a;
-        if (ncb > 1 && !conv_block_args(a, b, npb, plane_bytes + (planes == 2 ? (size_t)npb * 4 : 0), planes == 2 ? (long long)plane_bytes : -1, ab))
-            continue;
-        const int rc = planes == 3 ? launch_conv_split<3>(npb, ab, ntiles, st) : launch_conv_split<2>(npb, ab, ntiles, st);
+    for (int b = 0; b < p.ncb; ++b) {    // one launch; a wide layer: one per column block, same tiles and workgroups
+        ConvArgs ab;
+        if (!conv_block_args(a, p, b, ab)) continue;
+        const int rc = planes == 3 ? launch_conv_split<3>(ab, p, st) : launch_conv_split<2>(ab, p, st);
         if (rc) return rc;
     }
     return 0;
@@ -1744,12 +1817,7 @@ extern "C" int mmlf_conv2x2_split(const float *in, int cs_in, int K, const void 
 }
 
 // ------------------------------------------------------------------ f16 2-way split ("f16x3") entry points
-extern "C" int64_t mmlf_packed_filter_h2_bytes(int K, int N)
-{
-    const int np = x6_np(N);
-    if (np < 0 || K <= 0) return -1;
-    return (int64_t)((K + 7) / 8) * 8 * np * 16 + (int64_t)np * 4;      // + 1 / scale of every packed column
-}
+extern "C" int64_t mmlf_packed_filter_h2_bytes(int K, int N) { return packed_filter_bytes(2, K, N); }
 
 extern "C" int mmlf_pack_filter_h2(const float *w, void *packed, int Cout, int Cin, int variant, int dgrad,
                                    void *stream)
@@ -1794,12 +1862,9 @@ extern "C" int64_t mmlf_relu_mask_words(int B, int H, int W)
 
 extern "C" int mmlf_conv2x2_blocks(int K, int N, int B, int H, int W)
 {
-    const int np = x6_np(N);
-    if (np < 0 || K <= 0 || B <= 0 || H <= 0 || W <= 0) return -1;
-    const Grid g = make_grid(B, H, W);
-    const int nw = conv_sixteen_waves(2, np, g) ? 16 : 8;
-    if (conv_rs_shape(2, np, (K + 7) / 8, nw)) return (int)conv_rs_blocks(g.NQpad / 32);
-    return (int)conv_split_blocks(np / col_blocks(np) / 16, g.NQpad / (32 * nw), nw);      // (column blocks: the same grid each)
+    ConvPlan p;
+    if (K <= 0 || !conv_plan(2, (K + 7) / 8 * 8, N, B, H, W, p)) return -1;
+    return p.blocks;                                             // (column blocks: the same grid each)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1969,10 +2034,8 @@ extern "C" const char *mmlf_build_info(void)
 // (window pieces, tile counts, grids).  tests/test_bounds_audit.py holds every end against what the size queries of this
 // ABI tell the caller to allocate, over a sweep of shapes; the -DMMLF_BOUNDS_DEBUG build counts violations on the GPU.
 // Derivations (positions are grid positions q; a buffer of channel stride cs holds alloc = NQpad + P + 72 of them):
-//  conv, f16 split: the activation window of the LAST tile (first position NQpad - TILE) ends at position
-//    NQpad + P (one contiguous window of TILE + 1 + P positions, or two segments whose second one ends at P + 256);
-//    the last piece fetches a_tail positions only, the other lanes re-fetch the last of those.  The register-streamed
-//    kernel reads positions Q0 + 32 w + 16 mb + r16 + {0, 1, P, P + 1}: the same end.  Output: position q + out_shift,
+//  conv, f16 split: the launch geometry is the launch's own ConvPlan (its comment derives the last activation position
+//    fetched, NQpad + P).  Output: position q + out_shift,
 //    q < NQpad, n_store channels; the ReLU reference likewise.  Row maxima: rows up to the one behind the last position
 //    read (input) / written (output).  Mask words: [tile][8][8][64].  Statistics: [workgroup][2][N] doubles.
 //    A layer wider than 288 columns is two launches of this kind on column blocks (wide_np): the same tiles, windows and
@@ -1983,31 +2046,18 @@ extern "C" const char *mmlf_build_info(void)
 extern "C" int mmlf_audit_conv_h2(int cs_in, int K, int N, int cs_out, int N_store, int out_shift, int cs_ref, int B, int H, int W,
                                   int64_t *ends /* [MMLF_AUDIT_CONV_N] */)
 {
-    const int np = x6_np(N);
-    MMLF_CHECK_ARG(np > 0 && K > 0 && (K + 7) / 8 * 8 == cs_in && B > 0 && H > 0 && W > 0 && ends, "mmlf_audit_conv_h2: bad argument");
-    const Grid g = make_grid(B, H, W);
-    const int nw = conv_sixteen_waves(2, np, g) ? 16 : 8;
-    const int tile = 32 * nw, nchunk = cs_in / 8;
-    // the last activation position a launch fetches
-    long long last_in;
-    if (conv_rs_shape(2, np, nchunk, nw)) {
-        last_in = (g.NQpad - MMLF_TILE) + 32 * 7 + 16 + 15 + g.P + 1;
-    } else if (g.P + tile + 1 <= 640) {
-        const int pieces = (g.P + tile + 1 + 31) / 32, tail = (g.P + tile + 1) - 32 * (pieces - 1);
-        last_in = (g.NQpad - tile) + 32 * (pieces - 1) + tail - 1;
-    } else {
-        last_in = (g.NQpad - tile) + 320 + 32 * 8 + (g.P - 320) + 0;        // segment 1, piece 8, one position
-    }
+    ConvPlan p;
+    MMLF_CHECK_ARG(conv_plan(2, cs_in, N, B, H, W, p) && K > 0 && (K + 7) / 8 * 8 == cs_in && ends, "mmlf_audit_conv_h2: bad argument");
+    const Grid &g = p.g;
     const long long last_out = g.NQpad - 1 + out_shift;
-    const long long blocks = mmlf_conv2x2_blocks(K, N, B, H, W);
-    ends[0] = (last_in + 1) * cs_in * 4;                                      // in
-    ends[1] = (int64_t)nchunk * 8 * np * 16 + (int64_t)np * 4;                // packed (planes, then the columns' 1 / scale)
+    ends[0] = (p.last_in + 1) * cs_in * 4;                                    // in
+    ends[1] = (int64_t)p.ncb * p.block_bytes;                                 // packed (per block: planes, then the columns' 1 / scale)
     ends[2] = (int64_t)N * 4;                                                 // bias
     ends[3] = (last_out * cs_out + N_store) * 4;                              // out
     ends[4] = cs_ref ? (last_out * cs_ref + N_store) * 4 : 0;                 // relu_ref
     ends[5] = (MMLF_AMAX_HEAD + ((g.NQ - 1) / g.P + 1) + 1) * 4;              // in_amax: rows read by the last valid wave, + 1
     ends[6] = (MMLF_AMAX_HEAD + last_out / g.P + 1) * 4;                      // out_amax
-    ends[7] = blocks * 2 * N * 8;                                             // bn_partial (doubles)
+    ends[7] = (int64_t)p.blocks * 2 * N * 8;                                            // bn_partial (doubles)
     ends[8] = g.NQpad / MMLF_TILE * 4096 * 4;                                 // relu mask words (in or out)
     return 0;
 }
@@ -2044,7 +2094,7 @@ extern "C" int mmlf_conv3x3(const float *in, int cs_in, int K, const float *pack
     int nt = -1, ncb = 1;
     conv9_shape(N, &nt, &ncb);
     ConvArgs a;
-    Grid g;
+    const Grid g = make_grid(B, H, W);
     // the output goes to q + P + 1 (P = W + GRID_PAD), valid extent (H, W)
     if (conv_common_args("mmlf_conv3x3", 3, nt * ncb * 32, a, g, in, cs_in, K, packed, bias, N, out, cs_out, N_store,
                          W + GRID_PAD + 1, H, W, B, H, W, relu, relu_ref, cs_ref))

@@ -865,31 +865,77 @@ constexpr int WGRAD_MAX_COUT = 288, WGRAD_MAX_COUT_WIDE = 512;
 static inline int wgrad_col_blocks(int Cout) { return Cout > WGRAD_MAX_COUT ? 2 : 1; }
 static inline int wgrad_block_cout(int Cout, int b) { return b == 0 ? (Cout < WGRAD_MAX_COUT ? Cout : WGRAD_MAX_COUT) : Cout - WGRAD_MAX_COUT; }
 
-// partial sums of the position splits (largest of the kernels' layouts)
-static int64_t wgrad_partial_floats(int Cin, int Cout)
+// ---------------------------------------------------------------------------------------------
+// The launch plan of a weight gradient: per column block the kernel that runs it, its grid and the layout of its partial
+// sums -- computed HERE and nowhere else; the entry points launch and reduce by it, the workspace queries return its sizes
+// and the bounds audits derive their ends from it.
+// ---------------------------------------------------------------------------------------------
+struct WgradBlock {
+    int c0, cout;                 // output channels [c0, c0 + cout) of the layer
+    int nt;                       // the exact-f32 kernel on nt 32-column tiles (pick_nt), or 0: ...
+    Wgrad16Cfg cfg;               // ... the split-arithmetic kernel of this configuration
+    int nslice, nsplit;           // the launch grid (wgrad_block_map)
+    int CIP, NP;                  // rows and columns of the partial sums [nsplit][taps][CIP][NP] ...
+    int64_t part_floats;          // ... and their floats
+};
+struct WgradPlan {
+    int nblocks;
+    WgradBlock blk[2];
+    int64_t part_floats;          // partial sums of the largest block's launch
+    // floats of the workspace region the blocks' partial sums share, behind which the f16 split's chunk scales lie: the
+    // largest layout either kernel may choose for a block (so that one workspace serves every arithmetic path and batch)
+    int64_t scales_off;
+};
+// the exact-f32 kernel of a ks x ks filter: 32-channel ci slices (+1: the ones row that yields the bias gradient),
+// WgradF32Shape<ks>::BPS workgroups per slice
+static bool wgrad_f32_block(int ks, int Cin, int c0, int cout, WgradBlock &k)
 {
-    if (Cout > WGRAD_MAX_COUT) {
-        if (Cout > WGRAD_MAX_COUT_WIDE) return -1;
-        const int64_t n0 = wgrad_partial_floats(Cin, wgrad_block_cout(Cout, 0)), n1 = wgrad_partial_floats(Cin, wgrad_block_cout(Cout, 1));
-        return n0 > n1 ? n0 : n1;
+    k = {};
+    k.c0 = c0; k.cout = cout; k.nt = pick_nt(cout);
+    if (k.nt < 0) return false;
+    const int ci_slices = (Cin + 1 + 31) / 32;
+    k.nslice = (ks == 2 ? WgradF32Shape<2>::BPS : WgradF32Shape<3>::BPS) * ci_slices;
+    k.nsplit = wgrad_nsplit(k.nslice);
+    k.CIP = ci_slices * 32; k.NP = k.nt * 32;
+    k.part_floats = (int64_t)k.nsplit * ks * ks * k.CIP * k.NP;
+    return true;
+}
+static void wgrad_split_block(const Wgrad16Cfg &c, WgradBlock &k)
+{
+    k.nt = 0; k.cfg = c; k.nslice = c.nslice; k.nsplit = c.nsplit;
+    k.CIP = c.nslice * 16 * c.mb; k.NP = 16 * c.nb;
+    k.part_floats = (int64_t)k.nsplit * 4 * k.CIP * k.NP;
+}
+// 2x2.  planes: 0 = exact-f32 MFMA, 3 = bf16 split, 2 = f16 split; nchunks: 32-position chunks of the launch (< 0: none,
+// the plan is read for scales_off alone)
+static bool wgrad_plan(int planes, int Cin, int Cout, long long nchunks, WgradPlan &p)
+{
+    p = {};
+    if (Cout > WGRAD_MAX_COUT_WIDE) return false;
+    p.nblocks = wgrad_col_blocks(Cout);
+    for (int b = 0, c0 = 0; b < p.nblocks; c0 += p.blk[b++].cout) {
+        WgradBlock &k = p.blk[b];
+        WgradBlock largest = {};
+        Wgrad16Cfg c;
+        if (!wgrad_f32_block(2, Cin, c0, wgrad_block_cout(Cout, b), k)) return false;
+        int64_t sized = k.part_floats;
+        if (wgrad16_cfg(Cin, k.cout, -1, &c)) {
+            wgrad_split_block(c, largest);
+            if (largest.part_floats > sized) sized = largest.part_floats;
+        }
+        sized = (sized + 3) / 4 * 4;
+        if (sized > p.scales_off) p.scales_off = sized;
+        if (planes && wgrad16_cfg(Cin, k.cout, nchunks, &c)) wgrad_split_block(c, k);
+        if (k.part_floats > p.part_floats) p.part_floats = k.part_floats;
     }
-    const int nt = pick_nt(Cout);
-    if (nt < 0) return -1;
-    const int nslice = (Cin + 1 + 31) / 32;
-    int64_t n = (int64_t)wgrad_nsplit(nslice) * 4 * (nslice * 32) * (nt * 32);          // exact-f32 kernel
-    Wgrad16Cfg c;
-    if (wgrad16_cfg(Cin, Cout, -1, &c)) {                                                // split kernel
-        const int64_t m = (int64_t)c.nsplit * 4 * (c.nslice * 16 * c.mb) * (16 * c.nb);
-        if (m > n) n = m;
-    }
-    return (n + 3) / 4 * 4;
+    return true;
 }
 
 extern "C" int64_t mmlf_wgrad_workspace_floats(int Cin, int Cout, int B, int H, int W)
 {
-    const int64_t n = wgrad_partial_floats(Cin, Cout);
-    if (n < 0 || B <= 0 || H <= 0 || W <= 0) return -1;
-    return n + 2 * (make_grid(B, H, W).NQpad / WG_KQ) + 4;  // + the f16 split's per-chunk operand scales and the two tensor scales
+    WgradPlan p;
+    if (!wgrad_plan(0, Cin, Cout, -1, p) || B <= 0 || H <= 0 || W <= 0) return -1;
+    return p.scales_off + 2 * (make_grid(B, H, W).NQpad / WG_KQ) + 4;  // + the f16 split's per-chunk operand scales and the two tensor scales
 }
 
 template <int KS, int NT>
@@ -970,22 +1016,25 @@ static int wgrad_reduce(const WgradArgs &a, float *gw, float *gb, int Cin, int C
     return mmlf_launch_status(KS == 2 ? "mmlf_conv2x2_wgrad(reduce)" : "mmlf_conv3x3_wgrad(reduce)");
 }
 
-// exact-f32 weight gradient of a KS x KS filter: nt = pick_nt(Cout) 32-column tiles, 32-channel ci slices (+1: the ones row
-// that yields the bias gradient), BPS workgroups per slice
+// one planned block of a KS x KS weight gradient: its launch (planes: the split kernel's, when the plan chose it), then the
+// reduction of its partial sums into gw / gb (the block's rows of the OIHW master and of the bias gradient)
 template <int KS>
-static int wgrad_f32(WgradArgs &a, int nt, float *gw, float *gb, int Cin, int Cout, int variant, int accumulate, hipStream_t st)
+static int wgrad_run_block(WgradArgs &a, const WgradBlock &k, int planes, float *gw, float *gb, int Cin, int variant,
+                           int accumulate, hipStream_t st)
 {
-    const int ci_slices = (Cin + 1 + 31) / 32, nslice = WgradF32Shape<KS>::BPS * ci_slices;
-    wgrad_set_grid(a, nslice, wgrad_nsplit(nslice));
-    int rc;
-    switch (nt) {
+    wgrad_set_grid(a, k.nslice, k.nsplit);
+    int rc = 1;
+    if constexpr (KS == 2) {
+        if (!k.nt) rc = planes == 3 ? launch_wgrad_split<3>(k.cfg, a, st) : launch_wgrad_split<2>(k.cfg, a, st);
+    }
+    if (k.nt) switch (k.nt) {
     case 1: rc = launch_wgrad_f32<KS, 1>(a, st); break;
     case 3: rc = launch_wgrad_f32<KS, 3>(a, st); break;
     case 4: rc = launch_wgrad_f32<KS, 4>(a, st); break;
     default: rc = launch_wgrad_f32<KS, 9>(a, st); break;
     }
     if (rc) return rc;
-    return wgrad_reduce<KS>(a, gw, gb, Cin, Cout, ci_slices * 32, nt * 32, variant, accumulate, st);
+    return wgrad_reduce<KS>(a, gw, gb, Cin, k.cout, k.CIP, k.NP, variant, accumulate, st);
 }
 
 // planes: 0 = exact-f32 MFMA, 3 = bf16 split, 2 = f16 split (needs in_amax / g_amax)
@@ -1030,15 +1079,15 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
     MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_conv2x2_wgrad: bad variant");
     Grid gr = make_grid(B, H, W);
     MMLF_CHECK_ARG(g_shift >= 0 && g_shift <= gr.P + 1, "mmlf_conv2x2_wgrad: g_shift=%d", g_shift);
-    WgradArgs a = wgrad_args(in, cs_in, Cin, g, cs_g, g_shift, workspace, gr, grid_alloc_positions(gr),
-                             wgrad_partial_floats(Cin, Cout));
+    WgradPlan p;
+    MMLF_CHECK_ARG(wgrad_plan(planes, Cin, Cout, gr.NQpad / WG_KQ, p), "mmlf_conv2x2_wgrad: no launch plan");   // (refused above)
+    WgradArgs a = wgrad_args(in, cs_in, Cin, g, cs_g, g_shift, workspace, gr, grid_alloc_positions(gr), p.scales_off);
     a.in_amax = in_amax; a.g_amax = g_amax;
     hipStream_t st = (hipStream_t)stream;
-    Wgrad16Cfg c;
     if (planes == 2) {          // per-chunk operand scales, behind the partial sums in the workspace
         MMLF_CHECK_ARG(gr.NQpad + 2 * gr.P + 64 < (1ll << 31), "mmlf_conv2x2_wgrad_h2: batch x image too large");
         ChunkScaleArgs ca;
-        ca.in_amax = in_amax; ca.g_amax = g_amax; ca.out = workspace + wgrad_partial_floats(Cin, Cout);
+        ca.in_amax = in_amax; ca.g_amax = g_amax; ca.out = workspace + p.scales_off;
         ca.NQ = gr.NQ; ca.nchunks = a.nchunks; ca.P = gr.P; ca.g_shift = g_shift;
         ca.nrows = (int)amax_rows(gr);
         ca.divP = make_magic((unsigned)gr.P);
@@ -1046,20 +1095,13 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
         a.chunk_scales = ca.out;
     }
     const WgradArgs whole = a;
-    for (int b = 0, c0 = 0; b < wgrad_col_blocks(Cout); c0 += wgrad_block_cout(Cout, b), ++b) {
-        // column block b: output channels [c0, c0 + cb) of g, rows c0 .. of the OIHW master and of the bias gradient
-        const int cb = wgrad_block_cout(Cout, b);
+    for (int b = 0; b < p.nblocks; ++b) {
+        // column block b: output channels [c0, c0 + cout) of g, rows c0 .. of the OIHW master and of the bias gradient
+        const int c0 = p.blk[b].c0;
         a = whole;
         a.g = g + c0; a.g_cols = cs_g - c0; a.g_bytes = whole.g_bytes - 4ll * c0;
-        float *gwb = gw + (size_t)c0 * Cin * 4, *gbb = gb ? gb + c0 : nullptr;
-        int rc;
-        if (planes && wgrad16_cfg(Cin, cb, a.nchunks, &c)) {
-            wgrad_set_grid(a, c.nslice, c.nsplit);
-            rc = planes == 3 ? launch_wgrad_split<3>(c, a, st) : launch_wgrad_split<2>(c, a, st);
-            if (!rc) rc = wgrad_reduce<2>(a, gwb, gbb, Cin, cb, a.nslice * 16 * c.mb, 16 * c.nb, variant, accumulate, st);
-        } else {
-            rc = wgrad_f32<2>(a, pick_nt(cb), gwb, gbb, Cin, cb, variant, accumulate, st);
-        }
+        const int rc = wgrad_run_block<2>(a, p.blk[b], planes, gw + (size_t)c0 * Cin * 4, gb ? gb + c0 : nullptr, Cin, variant,
+                                          accumulate, st);
         if (rc) return rc;
     }
     return 0;
@@ -1176,25 +1218,20 @@ extern "C" int mmlf_conv2x2_wgrad_thin(const float *in, int cs_in, int Cin, cons
 extern "C" int mmlf_audit_wgrad_h2(int cs_in, int Cin, int cs_g, int Cout, int g_shift, int B, int H, int W,
                                    int64_t *ends /* [MMLF_AUDIT_WGRAD_N] */)
 {
-    Wgrad16Cfg c;
     MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0 && ends && Cin > 0 && Cout > 0, "mmlf_audit_wgrad_h2: bad argument");
     const Grid g = make_grid(B, H, W);
     const long long nchunks = g.NQpad / WG_KQ;
-    MMLF_CHECK_ARG(Cout <= WGRAD_MAX_COUT_WIDE, "mmlf_audit_wgrad_h2: Cout=%d", Cout);
-    int64_t part = 0;                                                         // partial sums of the largest column block's launch
-    for (int b = 0; b < wgrad_col_blocks(Cout); ++b) {
-        MMLF_CHECK_ARG(wgrad16_cfg(Cin, wgrad_block_cout(Cout, b), nchunks, &c), "mmlf_audit_wgrad_h2: Cout=%d", Cout);
-        const int64_t n = (int64_t)c.nsplit * 4 * (c.nslice * 16 * c.mb) * (16 * c.nb);
-        part = n > part ? n : part;
-    }
+    WgradPlan p;
+    MMLF_CHECK_ARG(wgrad_plan(2, Cin, Cout, nchunks, p) && !p.blk[0].nt && !p.blk[p.nblocks - 1].nt,     // (split kernels throughout)
+                   "mmlf_audit_wgrad_h2: Cout=%d", Cout);
     const long long last_c = (nchunks - 1) * WG_KQ;
     ends[0] = (last_c + g.P + 32 + 1) * cs_in * 4;                            // in: segment 1, row 32
     ends[1] = (last_c + g_shift + 31 + 1) * cs_g * 4;                         // g
     ends[2] = (int64_t)Cout * Cin * 4 * 4;                                    // gw (OIHW)
     ends[3] = (int64_t)Cout * 4;                                              // gb
-    ends[4] = (part                                                           // workspace: partial sums of this launch ...
-               > wgrad_partial_floats(Cin, Cout) ? -1                           // (must fit the sized region: else the scales overlap them)
-               : wgrad_partial_floats(Cin, Cout) + 2 * nchunks + 2) * 4;        // ... then the per-chunk and the two tensor scales
+    ends[4] = (p.part_floats                                                  // workspace: partial sums of this launch ...
+               > p.scales_off ? -1                                              // (must fit the sized region: else the scales overlap them)
+               : p.scales_off + 2 * nchunks + 2) * 4;                           // ... then the per-chunk and the two tensor scales
     ends[5] = (MMLF_AMAX_HEAD + amax_rows(g)) * 4;                            // in_amax (the scale kernel clamps rows to amax_rows - 1)
     ends[6] = ends[5];                                                        // g_amax
     return 0;
@@ -1204,22 +1241,14 @@ extern "C" int mmlf_audit_wgrad_h2(int cs_in, int Cin, int cs_g, int Cout, int g
 // weight + bias gradient of the 3x3 ("same", pad 1) convolution, exact-f32 MFMA (wgrad9tap_kernel = wgrad_f32_taps<3, NT>
 // above, g_shift = P + 1): entry points
 // ---------------------------------------------------------------------------------------------
-// launch layout of the 3x3 weight gradient: 3 * (ci slices) x position splits
-struct Wgrad9Cfg { int nt, nslice, nsplit; };
-static inline bool wgrad9_cfg(int Cin, int Cout, Wgrad9Cfg *c)
-{
-    c->nt = pick_nt(Cout);
-    if (c->nt < 0 || Cin <= 0) return false;
-    c->nslice = 3 * ((Cin + 1 + 31) / 32);      // +1: the ones row that yields the bias gradient
-    c->nsplit = wgrad_nsplit(c->nslice);
-    return true;
-}
+// launch layout of the 3x3 weight gradient: one block (wgrad_f32_block), 3 * (ci slices) x position splits
+static inline bool wgrad9_plan(int Cin, int Cout, WgradBlock &k) { return Cin > 0 && wgrad_f32_block(3, Cin, 0, Cout, k); }
 
 extern "C" int64_t mmlf_wgrad3x3_workspace_floats(int Cin, int Cout, int B, int H, int W)
 {
-    Wgrad9Cfg c;
-    if (!wgrad9_cfg(Cin, Cout, &c) || B <= 0 || H <= 0 || W <= 0) return -1;
-    return (int64_t)c.nsplit * 9 * (c.nslice / 3 * 32) * (c.nt * 32);
+    WgradBlock k;
+    if (!wgrad9_plan(Cin, Cout, k) || B <= 0 || H <= 0 || W <= 0) return -1;
+    return k.part_floats;
 }
 
 extern "C" int mmlf_conv3x3_wgrad(const float *in, int cs_in, int Cin, const float *g, int cs_g, int Cout, float *gw_oihw,
@@ -1230,28 +1259,27 @@ extern "C" int mmlf_conv3x3_wgrad(const float *in, int cs_in, int Cin, const flo
     MMLF_CHECK_ARG(cs_in % 4 == 0 && cs_g % 4 == 0, "mmlf_conv3x3_wgrad: strides must be multiples of 4");
     MMLF_CHECK_ARG(Cin > 0 && Cin <= cs_in && Cout > 0 && Cout <= cs_g, "mmlf_conv3x3_wgrad: channels vs strides");
     MMLF_CHECK_ARG(variant >= 0 && variant <= 2, "mmlf_conv3x3_wgrad: bad variant");
-    Wgrad9Cfg c;
-    MMLF_CHECK_ARG(wgrad9_cfg(Cin, Cout, &c), "mmlf_conv3x3_wgrad: Cout=%d not supported", Cout);
+    WgradBlock k;
+    MMLF_CHECK_ARG(wgrad9_plan(Cin, Cout, k), "mmlf_conv3x3_wgrad: Cout=%d not supported", Cout);
     const Grid gr = make_grid(B, H, W);
     MMLF_CHECK_ARG(gr.NQpad + 2 * gr.P + 64 < (1ll << 31), "mmlf_conv3x3_wgrad: batch x image too large");
-    WgradArgs a = wgrad_args(in, cs_in, Cin, g, cs_g, gr.P + 1, workspace, gr, grid_alloc_positions_k3(gr),
-                             mmlf_wgrad3x3_workspace_floats(Cin, Cout, B, H, W));
-    return wgrad_f32<3>(a, c.nt, gw_oihw, gb, Cin, Cout, variant, accumulate, (hipStream_t)stream);
+    WgradArgs a = wgrad_args(in, cs_in, Cin, g, cs_g, gr.P + 1, workspace, gr, grid_alloc_positions_k3(gr), k.part_floats);
+    return wgrad_run_block<3>(a, k, 0, gw_oihw, gb, Cin, variant, accumulate, (hipStream_t)stream);
 }
 
 // Bounds audit of one mmlf_conv3x3_wgrad launch (ends[MMLF_AUDIT_WG_IN .. MMLF_AUDIT_WG_WORKSPACE]): chunk c stages
 // in[32 c + dy P .. + 33] and g[32 c + P + 1 .. + 31], c < NQpad / 32.
 extern "C" int mmlf_audit_wgrad3x3(int cs_in, int Cin, int cs_g, int Cout, int B, int H, int W, int64_t *ends /* [5] */)
 {
-    Wgrad9Cfg c;
-    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0 && ends && wgrad9_cfg(Cin, Cout, &c), "mmlf_audit_wgrad3x3: bad argument");
+    WgradBlock k;
+    MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0 && ends && wgrad9_plan(Cin, Cout, k), "mmlf_audit_wgrad3x3: bad argument");
     const Grid g = make_grid(B, H, W);
     const long long last_c = g.NQpad - WG_KQ;
-    const int slice_end = c.nslice / 3 * 32;                                  // channels the last slice stages (< cs_in only)
-    ends[0] = ((last_c + 2 * g.P + WG_KQ + 1) * cs_in + (slice_end < cs_in ? slice_end : cs_in)) * 4;   // in
-    ends[1] = ((last_c + g.P + 1 + WG_KQ - 1) * cs_g + (c.nt * 32 < cs_g ? c.nt * 32 : cs_g)) * 4;     // g
+    // (k.CIP: channels the last slice stages, k.NP: gradient columns a workgroup stages -- below the strides only)
+    ends[0] = ((last_c + 2 * g.P + WG_KQ + 1) * cs_in + (k.CIP < cs_in ? k.CIP : cs_in)) * 4;   // in
+    ends[1] = ((last_c + g.P + 1 + WG_KQ - 1) * cs_g + (k.NP < cs_g ? k.NP : cs_g)) * 4;        // g
     ends[2] = (int64_t)Cout * Cin * 9 * 4;                                    // gw (OIHW)
     ends[3] = (int64_t)Cout * 4;                                              // gb
-    ends[4] = mmlf_wgrad3x3_workspace_floats(Cin, Cout, B, H, W) * 4;         // workspace
+    ends[4] = k.part_floats * 4;                                              // workspace
     return 0;
 }

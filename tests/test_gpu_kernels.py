@@ -462,6 +462,45 @@ def test_fused_batchnorm_statistics_match_the_two_pass_form(cin, cout):
     assert torch.equal(geo.amax_canonical(z.absmax), geo.amax_of(z, cs_out))      # the conv epilogue's tensor and grid-row maxima (P >= 32: exact)
 
 
+# pitches 127 | 128 (sixteen waves | eight, where the register-streamed kernel takes the 70-wide layer) and 383 | 384 (one
+# activation window | two segments), and a frame of fewer tiles than the chip has CUs
+@pytest.mark.parametrize('B,H,W', [(1, 3, 5), (2, 9, 125), (2, 9, 126), (1, 2, 381), (1, 2, 382)])
+@pytest.mark.parametrize('K,N', [(70, 70), (280, 280), (296, 296)])
+def test_size_query_counts_the_statistics_slabs_a_launch_writes(K, N, B, H, W):
+    """mmlf_conv2x2_blocks is what engine._block_fwd tells mmlf_bn_stats_finalize to sum: it must be the number of [2][N]
+    slabs the launch (both column blocks of a wide layer) writes -- no slab fewer, none more -- and the slabs must add up to
+    the sums of the stored output.  Operands are non-negative, so a channel's sum is as large as its terms and the
+    float32 sums a wave takes over its 32 positions stay within the bar of the fused-statistics test above."""
+    from mmlf_amd import engine, _lib
+    from mmlf_amd._lib import call, ptr
+    dev = _dev()
+    geo = engine.Geometry(B, H, W)
+    cs_in, cs_out = engine.cs_of(K), engine.cs_of(N)
+    gen = torch.Generator(device=dev).manual_seed(K + W)
+    x = torch.zeros(geo.alloc * cs_in, device=dev)
+    x[:geo.NQ * cs_in].view(B, geo.R, geo.P, cs_in)[:, :H + 1, :W + 1, :K] = torch.rand((B, H + 1, W + 1, K), device=dev, generator=gen)
+    w = torch.rand((N, K, 2, 2), device=dev, generator=gen) * 0.05
+    bias = torch.rand(N, device=dev, generator=gen)
+    pk = torch.empty(int(_lib.load().mmlf_packed_filter_h2_bytes(cs_in, N)) // 4, device=dev)
+    call('mmlf_pack_filter_h2', ptr(w), ptr(pk), N, K, 0, 0, _lib.stream_ptr())
+    amax = geo.amax_of(x, cs_in)
+    z = geo.buf(cs_out, dev)
+    blocks = int(_lib.load().mmlf_conv2x2_blocks(K, N, B, H, W))
+    assert blocks >= 1
+    partial = torch.full((blocks + 1, 2, N), float('nan'), dtype=torch.float64, device=dev)
+    call('mmlf_conv2x2_h2', ptr(x), cs_in, K, ptr(pk), ptr(bias), N, ptr(z), cs_out, cs_out, geo.P + 1, H, W,
+         B, H, W, 0, None, 0, ptr(amax), ptr(z.absmax), ptr(partial), None, None, _lib.stream_ptr())
+    finite = torch.isfinite(partial).all(dim=2).all(dim=1).cpu().numpy()
+    assert finite[:blocks].all() and not finite[blocks], (blocks, finite)
+    assert torch.isnan(partial[blocks]).all()
+    zz = z.view(geo.alloc, cs_out)[:, :N].double()
+    ref = torch.stack([zz.sum(0), (zz * zz).sum(0)]).cpu().numpy()
+    got = partial[:blocks].sum(0).cpu().numpy()
+    print(f'{K}->{N} {B}x{H}x{W}: {blocks} slabs, worst relative difference {np.abs(got / ref - 1).max():.3g}')
+    assert ref[0].min() > 0
+    np.testing.assert_allclose(got, ref, rtol=2e-6, atol=1e-7)
+
+
 def test_slack_and_amax_zeroing():
     from mmlf_amd import engine, _lib
     from mmlf_amd._lib import call, ptr

@@ -70,7 +70,8 @@ def model_of(net, chs, oc):
     return model.to(DEV)
 
 
-def run(net, chs, oc, pas, mode='f16x3', overlap=True, packed=False, extents=False):
+def run(net, chs, oc, pas, mode='f16x3', overlap=True, packed=False, extents=False, frame=(B, H, W)):
+    B, H, W = frame
     train, save = PASSES[pas]
     engine.CONV_MODE, engine.OVERLAP_WGRAD, engine.CHECK_EXTENTS = mode, overlap, extents
     engine.EXTENT_CHECKS = 0
@@ -116,6 +117,14 @@ def configurations():
     yield 'packed: k2bn chs=6 oc=2 eval_folded', ('k2bn', 6, 2, 'eval_folded', 'f16x3', True, True)
     for net, pas in (('k2bn', 'train_saved'), ('k2nobn', 'train_saved'), ('k3bn', 'train_saved'), ('k2bn', 'eval_folded')):
         yield f'extents: {net} chs=32 oc=2 {pas}', (net, 32, 2, pas, 'f16x3', True, False, True)
+    # the default width (70: the 280-wide G = 18 launches, 80-column kernels over 4 and 9 chunks) and column blocks (96: 384 wide)
+    for net, chs, oc, pas in itertools.product(('k2bn', 'k2nobn'), (70, 96), HEADS, PASSES):
+        for mode in ('f16x3', 'bf16x6', 'f32'):
+            for overlap in ((True, False) if PASSES[pas][1] else (True,)):
+                yield f'{net} chs={chs} oc={oc} {pas} {mode} overlap={int(overlap)}', (net, chs, oc, pas, mode, overlap)
+    # ... and a pitch of 128, where the sixteen-wave tile's window no longer fits: the register-streamed launches
+    for net, pas in itertools.product(('k2bn', 'k2nobn'), ('train_saved', 'eval_folded')):
+        yield f'pitch 128: {net} chs=70 oc=1 {pas}', (net, 70, 1, pas, 'f16x3', True, False, False, (1, 3, 126))
 
 
 def diff(a, b):
