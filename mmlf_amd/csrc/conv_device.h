@@ -119,6 +119,9 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // XCD-aware tile order): with n < 256 the conv / weight-gradient grids leave 256 - n CUs without a resident workgroup,
 // which is where a collective's kernels can run BESIDE them under data parallelism (the wide kernels take 151 KB of a
 // CU's 160 KB LDS: nothing else fits on a CU they occupy).  bench.py reports the value in config.conv_cus.
+// The wide weight gradient is one of these launches: its RESIDENT grid -- one workgroup per CU, walking the (slice, split)
+// items (wgrad_map.h wgrad_wide_grid) -- is 8 * (n / 8) workgroups, so the cap bounds the CUs that kernel holds as well (it
+// used to bound only the number of position splits a small batch is cut into).
 static int device_cus()
 {
     static int cus[64] = {};                 // per device ordinal (a benign race only repeats the query)

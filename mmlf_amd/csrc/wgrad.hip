@@ -4,6 +4,7 @@
 // gfx950 only.  Arithmetic replaced: the weight / bias gradient of nn.Conv2d(k=2, pad 1|0), reference
 // mmlf/model/feed_forward.py:123,125 under autograd (mmlf/train/cli.py:257).
 #include "conv_device.h"
+#include "wgrad_map.h"
 
 #ifdef MMLF_BOUNDS_DEBUG
 int mmlf_oob_counts_wgrad(unsigned long long *host8, int reset)
@@ -26,6 +27,7 @@ struct WgradArgs {
     float *part;          // [nsplit][4][CIP][NP]
     long long NQpad;
     int cs_in, cin, cs_g, g_shift, P, nsplit, nslice, chunks_per_split, nchunks;
+    int items;            // blocks of the one-shot launch, wgrad_grid_blocks(nslice, nsplit): what the persistent wide kernel walks
     int g_cols;           // channels of a row of g from the pointer on: cs_g, less the offset of a column block (wgrad_impl)
     const float *in_amax, *g_amax;   // f16 split: amax arrays of in and g (common.h)
     const float *chunk_scales;       // f16 split: [nchunks][2] power-of-two operand scales (wgrad_chunk_scales_kernel)
@@ -34,32 +36,7 @@ struct WgradArgs {
                                                 // the MMLF_BOUNDS_DEBUG build only
 };
 
-// Block -> (slice, position split).  Blocks b, b + 8, ... land on one XCD (round-robin dispatch): the slices of one split are
-// placed there and share its L2 for their gradient reads.  nsplit need not be a multiple of 8: the 8 * (nsplit / 8) regular
-// splits are numbered as they always were (same partial-sum order), the slices of the remaining ones are dealt behind them,
-// `per` blocks to an XCD, consecutive slices together (their gradient reads come from memory once per XCD they touch: a few
-// percent of the launch's reads at 2 of 42 splits).
-__device__ __forceinline__ bool wgrad_block_map(const WgradArgs &a, int &slice, int &split)
-{
-    const int b = blockIdx.x, x = b & 7, j = b >> 3;
-    const int reg = (a.nsplit >> 3) * a.nslice;           // regular blocks per XCD
-    if (j < reg) {
-        slice = j % a.nslice;
-        split = (j / a.nslice) * 8 + x;
-        return true;
-    }
-    const int left = (a.nsplit & 7) * a.nslice, per = (left + 7) >> 3;
-    const int m = x * per + (j - reg);
-    slice = m % a.nslice;
-    split = (a.nsplit & ~7) + m / a.nslice;
-    return m < left;
-}
-
-static inline unsigned wgrad_grid_blocks(int nslice, int nsplit)
-{
-    return 8u * (unsigned)((nsplit >> 3) * nslice + ((nsplit & 7) * nslice + 7) / 8);
-}
-
+// block -> (slice, split) item, the wide launch's splits and its grid: wgrad_map.h (shared with tools/wgrad_items.hip)
 #define WG_KQ 32  // positions per chunk
 
 // Exact-f32 weight + bias gradient of both filter sizes: one body on KS = 2 (wgrad4tap_kernel) or 3 (wgrad9tap_kernel),
@@ -100,7 +77,7 @@ __device__ __forceinline__ void wgrad_f32_taps(const WgradArgs &a)
     const int lane = tid & 63, wv = tid >> 6;
     const int i = lane & 31, kh = lane >> 5;
     int sd, split;
-    if (!wgrad_block_map(a, sd, split)) return;
+    if (!wgrad_block_map(blockIdx.x, a.nslice, a.nsplit, sd, split)) return;
     const int slice = sd / BPS, dy = sd - BPS * slice;
     const int ci0 = slice * 32;
     int c_begin = split * a.chunks_per_split;
@@ -374,7 +351,7 @@ __global__ __launch_bounds__(256, 2) void wgrad4tap_x6n_kernel(WgradArgs a)
     const int lane = tid & 63, t = tid >> 6;
     const int r16 = lane & 15, q4 = lane >> 4;
     int slice, split;
-    if (!wgrad_block_map(a, slice, split)) return;
+    if (!wgrad_block_map(blockIdx.x, a.nslice, a.nsplit, slice, split)) return;
     const int ci0 = slice * 16 * MB;
     int c_begin = split * a.chunks_per_split;
     int c_end = c_begin + a.chunks_per_split;
@@ -527,21 +504,7 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t = w & 3, h = w >> 2;
-    const int r16 = lane & 15, q4 = lane >> 4;
-    int slice, split;
-    if (!wgrad_block_map(a, slice, split)) return;
-    const int ci0 = slice * 16 * MB;
-    const int c_begin = split * a.chunks_per_split;
-    int c_end = c_begin + a.chunks_per_split;
-    if (c_end > a.nchunks) c_end = a.nchunks;
-
-    f32x4 acc[MB][NBH];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NBH; ++nb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[mb][nb][r] = 0.f;
+    const int q4 = lane >> 4;
 
     float4 ra[NA], rg[NG];
     // Input channels past cs_in and gradient columns past cs_g (the slices' and the 288 columns' padding) are staged as COPIES of
@@ -562,6 +525,8 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
     // inside an LDS buffer.  Round 5: with the addresses recomputed from 64-bit terms in the loop and the padding channels
     // zero-filled by selects, a chunk had 136 vector instructions per wave next to its 81 MFMAs; the vector-issue port is what
     // this kernel runs out of (each one removed is ~0.01 ms per launch: profiles/r05_kbench_wgrad_zeropad.log).
+    // (of these, the gradient's and the LDS offsets belong to the lane alone and are formed once per workgroup; the activation
+    // offsets carry the item's input-channel slice and are formed once per item, below)
     unsigned ga_off[NA], gg_off[NG];
     int la_off[NA], lg_off[NG], a_ch[NA];
 #pragma unroll
@@ -569,8 +534,6 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
         const int idx = min(tid + 512 * j, 66 * FA - 1);
         const int row = idx / FA, f = idx - row * FA;
         const int seg = row >= 33, pix = row - 33 * seg;
-        a_ch[j] = ci0 + 4 * f;
-        ga_off[j] = (unsigned)((seg * a.P + pix) * a.cs_in + min(ci0 + 4 * f, a.cs_in - 4)) * 4u;
         la_off[j] = seg * PL * A_PLANE + pix * ROWA + 8 * f;
     }
 #pragma unroll
@@ -617,12 +580,54 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
 #define WW_STORE_G(j, dst) split_store4_pl<PL>(rg[j], st_sg, (dst) + lg_off[j], G_PLANE)
 
     const int tq = (lane & 15) >> 2, tp = lane & 3;
-    const int a_off = (t >> 1) * PL * A_PLANE + ((t & 1) + 4 * q4 + tq) * ROWA + 8 * tp;
-    const int g_off = A_BYTES + (4 * q4 + tq) * ROWG + 8 * tp + 32 * NBH * h;
+    int a_off = (t >> 1) * PL * A_PLANE + ((t & 1) + 4 * q4 + tq) * ROWA + 8 * tp;
+    int g_off = A_BYTES + (4 * q4 + tq) * ROWG + 8 * tp + 32 * NBH * h;
+
+    // PERSISTENT over the (slice, split) items of the launch: workgroup blockIdx.x runs the blocks b = blockIdx.x,
+    // + gridDim.x, ... of the one-shot launch, each exactly as that block ran it -- accumulators zeroed per item, its own
+    // partial sums written in its own epilogue -- so the partial sums and the gradient are the one-shot launch's bit for bit.
+    // With gridDim.x = items (MMLF_WGRAD_PERSIST=0, and every launch of no more items than CUs) it IS the one-shot launch.
+    // b is wave-uniform: the loop state lives in scalar registers.  (The item's body keeps the indentation it had as the
+    // whole kernel.)
+    for (int b = blockIdx.x; b < a.items; b += gridDim.x) {
+    int slice, split;
+    if (!wgrad_block_map(b, a.nslice, a.nsplit, slice, split)) continue;      // (workgroup-uniform)
+    const int ci0 = slice * 16 * MB;
+    const int c_begin = split * a.chunks_per_split;
+    int c_end = c_begin + a.chunks_per_split;
+    if (c_end > a.nchunks) c_end = a.nchunks;
+
+    f32x4 acc[MB][NBH];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < NBH; ++nb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[mb][nb][r] = 0.f;
+    // (the thread index and the lane's staging / fragment offsets are made opaque per item, here and at the epilogue: what
+    // depends on the lane alone would otherwise be hoisted out of the item loop and held in registers across the chunk loop
+    // -- 254 of them instead of 226, past the 232 the BatchNorm pairing leaves this kernel; EXPERIMENTS section 8, constraint (i))
+#pragma unroll
+    for (int j = 0; j < NA; ++j) asm volatile("" : "+v"(la_off[j]));
+#pragma unroll
+    for (int j = 0; j < NG; ++j) asm volatile("" : "+v"(lg_off[j]), "+v"(gg_off[j]));
+    asm volatile("" : "+v"(a_off), "+v"(g_off));
+    int tid_i;               // = tid, rebuilt from the lane count and the scalar wave index: tid itself need not stay live
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(tid_i));
+    tid_i += 64 * w;
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+        const int idx = min(tid_i + 512 * j, 66 * FA - 1);
+        const int row = idx / FA, f = idx - row * FA;
+        const int seg = row >= 33, pix = row - 33 * seg;
+        a_ch[j] = ci0 + 4 * f;
+        ga_off[j] = (unsigned)((seg * a.P + pix) * a.cs_in + min(ci0 + 4 * f, a.cs_in - 4)) * 4u;
+    }
 
     float st_sa = 1.f, st_sg = 1.f;          // operand scales of the chunk being staged
     if (c_begin < c_end) {
         WW_GLOAD(c_begin);
+        __syncthreads();        // the previous item's last chunk may still be being read from the buffers staged into next
         wgrad_chunk_scale<PL>(a, c_begin, st_sa, st_sg);
 #pragma unroll
         for (int j = 0; j < NA; ++j) WW_STORE_A(j, smem);
@@ -716,28 +721,33 @@ __global__ __launch_bounds__(512, 2) void wgrad4tap_x6w_kernel(WgradArgs a)
             (void)c;
             WW_CHUNK(false, false);          // last chunk: nothing left to stage
         }
-#undef WW_CHUNK
-#undef WW_TERM
     }
-#undef WW_GLOAD
-#undef WW_GLOAD_A
-#undef WW_GLOAD_G
-#undef WW_STORE_A
-#undef WW_STORE_G
+    // (an item whose split holds no chunks writes its zero partial sums like any other: the reduction reads every split)
     constexpr int NP = 16 * NB;
     const int CIP = a.nslice * 16 * MB;
     float *pp = a.part + ((size_t)(split * 4 + t) * CIP + ci0) * NP + 16 * NBH * h;
+    int tid_e;               // = lane, as above
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(tid_e));
+    const int r16e = tid_e & 15, q4e = (tid_e & 63) >> 4;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
         for (int nb = 0; nb < NBH; ++nb)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int row = 16 * mb + 4 * q4 + r;      // the ones row (bias gradient) carries no input scale
+                const int row = 16 * mb + 4 * q4e + r;     // the ones row (bias gradient) carries no input scale
                 const float un = (ci0 + row == a.cin ? 1.f : sc.inv_sa) * sc.inv_sg;
-                MMLF_OOB(OOB_WG_PART, (long long)(pp - a.part) + (long long)row * NP + 16 * nb + r16 >= a.part_floats);
-                pp[(size_t)row * NP + 16 * nb + r16] = acc[mb][nb][r] * un;
+                MMLF_OOB(OOB_WG_PART, (long long)(pp - a.part) + (long long)row * NP + 16 * nb + r16e >= a.part_floats);
+                pp[(size_t)row * NP + 16 * nb + r16e] = acc[mb][nb][r] * un;
             }
+    }
+#undef WW_CHUNK
+#undef WW_TERM
+#undef WW_GLOAD
+#undef WW_GLOAD_A
+#undef WW_GLOAD_G
+#undef WW_STORE_A
+#undef WW_STORE_G
 }
 
 // sum the position splits and scatter to the OIHW master gradient (+ bias gradient).  One thread per output element:
@@ -833,18 +843,9 @@ static inline bool wgrad16_cfg(int Cin, int Cout, long long nchunks, Wgrad16Cfg 
 {
     if (Cout <= 0 || Cout > 288) return false;
     c->nb = Cout <= 32 ? 2 : Cout <= 80 ? 5 : Cout <= 128 ? 8 : 18;
-    if (c->nb == 18) {           // wgrad4tap_x6w_kernel: one 512-thread workgroup per CU, three even rounds
+    if (c->nb == 18) {           // wgrad4tap_x6w_kernel: one 512-thread workgroup per CU, persistent over the items (wgrad_map.h)
         c->mb = 3;
-        c->nslice = (Cin + 1 + 47) / 48;
-        // Small batches: ONE round on 256 CUs (42 splits = 252 workgroups at six slices; a third of the partial sums to
-        // write and reduce: -2...-4 % per launch at 64 patches, +0.9 % per 64-patch step).  From ~150 patches on, three
-        // even rounds of 256 (128 splits) are 0.8 % faster inside the step (profiles/r04_wgrad_nsplit.log).
-        // (the workspace is sized by the LARGER of the two counts at 256 CUs: a part with fewer CUs only lowers one_round)
-        const int cus = nchunks < 0 ? 256 : (device_cus() < 256 ? device_cus() : 256);
-        const int one_round = cus / c->nslice, three_rounds = (768 / c->nslice + 7) / 8 * 8;
-        c->nsplit = nchunks < 0 ? (one_round > three_rounds ? one_round : three_rounds)
-                                : (nchunks >= 42 * 1024 ? three_rounds : one_round);
-        if (c->nsplit < 8) c->nsplit = 8;
+        wgrad_wide_splits(Cin, nchunks, device_cus(), c->nslice, c->nsplit);
     } else {                     // wgrad4tap_x6n_kernel: two 256-thread workgroups per CU
         c->mb = (c->nb <= 5 && Cin + 1 > 32 && Cin + 1 <= 80) ? 5 : 2;
         // 128 columns (the 108-class DPP head): 48-row slices from 128 input channels on -- six slices of 281 rows instead of
@@ -959,6 +960,13 @@ static int launch_wgrad16(const WgradArgs &a, hipStream_t st)
     return mmlf_launch_status("mmlf_conv2x2_wgrad_split");
 }
 
+// MMLF_WGRAD_PERSIST=0 (read once per process): the wide kernel as one workgroup per item (wgrad_map.h wgrad_wide_grid)
+static bool wgrad_persist()
+{
+    static const bool on = [] { const char *e = getenv("MMLF_WGRAD_PERSIST"); return !e || atoi(e) != 0; }();
+    return on;
+}
+
 template <int PL>
 static int launch_wgrad_wide(const WgradArgs &a, hipStream_t st)
 {
@@ -966,7 +974,7 @@ static int launch_wgrad_wide(const WgradArgs &a, hipStream_t st)
     static PerDeviceOnce attr_once;
     if (attr_once.run([] { return mmlf_allow_lds(reinterpret_cast<const void *>(wgrad4tap_x6w_kernel<3, 9, PL>), lds, "mmlf_conv2x2_wgrad_split(wide)"); }))
         return 1;
-    hipLaunchKernelGGL((wgrad4tap_x6w_kernel<3, 9, PL>), dim3(wgrad_grid_blocks(a.nslice, a.nsplit)), dim3(512), lds, st, a);
+    hipLaunchKernelGGL((wgrad4tap_x6w_kernel<3, 9, PL>), dim3(wgrad_wide_grid(a.items, device_cus(), wgrad_persist())), dim3(512), lds, st, a);
     return mmlf_launch_status("mmlf_conv2x2_wgrad_split");
 }
 
@@ -1003,6 +1011,7 @@ static void wgrad_set_grid(WgradArgs &a, int nslice, int nsplit)
     a.nslice = nslice;
     a.nsplit = nsplit;
     a.chunks_per_split = (a.nchunks + nsplit - 1) / nsplit;
+    a.items = (int)wgrad_grid_blocks(nslice, nsplit);
 }
 
 // sum the launch's partial sums [a.nsplit][KS*KS][CIP][NP] into the OIHW gradient
