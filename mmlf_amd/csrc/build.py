@@ -16,7 +16,7 @@ def stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = SOURCES + ['common.h', 'conv_device.h', 'wgrad_map.h', 'build.py', os.path.join('..', '..', 'include', 'mmlf_hip.h')]
+    deps = SOURCES + ['common.h', 'conv_device.h', 'wgrad_map.h', 'row_walk.h', 'build.py', os.path.join('..', '..', 'include', 'mmlf_hip.h')]
     return any(os.path.getmtime(os.path.join(HERE, d)) > t for d in deps)
 
 
@@ -32,7 +32,7 @@ def source_revision():
         return 'unknown'          # (no git on the GPU box's snapshot: the library that travels there was built here)
 
 
-HASHED = SOURCES + ['common.h', 'conv_device.h', 'wgrad_map.h', os.path.join('..', '..', 'include', 'mmlf_hip.h')]
+HASHED = SOURCES + ['common.h', 'conv_device.h', 'wgrad_map.h', 'row_walk.h', os.path.join('..', '..', 'include', 'mmlf_hip.h')]
 
 
 def source_hash():

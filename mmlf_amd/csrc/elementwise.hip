@@ -2,6 +2,7 @@
 // backward, layout pack/unpack, UPR / DPP heads, losses, Adam, Shift and the ensemble reduce.
 // gfx950 only.  Reference call sites are cited per entry point in include/mmlf_hip.h.
 #include "common.h"
+#include "row_walk.h"
 #include "../../include/mmlf_hip.h"
 
 thread_local char g_mmlf_err[512] = "";
@@ -58,18 +59,9 @@ template <> struct VecIO<4> {
             *reinterpret_cast<float2 *>(p + 2) = make_float2(o[2], o[3]);
         }
     }
-    // streamed once: keep it out of the way of data that is re-read
-    static __device__ __forceinline__ void load_nt(const float *p, float *o)
-    {
-        if (aligned(p)) {
-            typedef float f4 __attribute__((ext_vector_type(4)));
-            const f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(p));
-            o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
-        } else {
-            load(p, o);
-        }
-    }
-    // the same with the alignment decided once per launch by the caller (a scalar branch, no per-lane address test)
+    // streamed once: keep it out of the way of data that is re-read.  The alignment may be decided once per launch by the
+    // caller (a scalar branch, no per-lane address test)
+    static __device__ __forceinline__ void load_nt(const float *p, float *o) { load_nt(p, o, aligned(p)); }
     static __device__ __forceinline__ void load_nt(const float *p, float *o, bool is_aligned)
     {
         if (is_aligned) {
@@ -104,8 +96,8 @@ __device__ __forceinline__ void bn_reduce_body(const float *__restrict__ z, int 
                                                         double *__restrict__ partial, int B, int H, int W)
 {
     const int P = W + GRID_PAD, R = H + GRID_PAD;
-    const int cvn = (C + V - 1) / V;            // channel groups that hold real channels
-    const int ppi = 256 / cvn;                  // positions per iteration
+    int cvn, ppi;                               // channel groups that hold real channels, positions per iteration
+    reduce_walk(C, V, cvn, ppi);
     const int tid = threadIdx.x;
     const int pl = tid / cvn, cg = tid - pl * cvn;
     const bool active = pl < ppi;
@@ -297,6 +289,27 @@ __global__ void fold_bn_kernel(const float *__restrict__ w, const float *__restr
 // row-wise elementwise kernels: one block per grid row (b, y), y in [0, R)
 // MODE 0: y = relu(z*scale+shift) (interior) | MODE 1: dz = k1*g - k2 - k3*(z-mean), g = gy*(u>0)
 // ---------------------------------------------------------------------------------------------
+// What the row kernels share: a block takes grid rows blockIdx.x, + gridDim.x, ... (launched with one block per row); a
+// thread walks the row's (position, channel group) pairs without divisions (row_walk.h, where the bound on every index
+// of these kernels is stated) and calls op(q, interior, cg, mx) at each -- q = row * P + x, the position's index in the
+// grid; interior: not on the zero border; mx: the thread's largest |value written| so far, which op raises -- and the
+// block raises the row's amax entry once.
+template <class Op>
+__device__ __forceinline__ void for_each_row_pair(int cvn, int H, int W, int nrows, float *__restrict__ amax, Op op)
+{
+    const int P = W + GRID_PAD, R = H + GRID_PAD;
+    const RowWalk w = row_walk(cvn);
+    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
+        const size_t base = (size_t)row * P;
+        const bool row_in = grid_row_interior(row, R, H);
+        float mx = 0.f;
+        int x, cg;
+        for (bool in = row_walk_start(w, threadIdx.x, P, x, cg); in; in = row_walk_step(w, P, x, cg))
+            op(base + x, row_in && grid_pos_interior(x, W), cg, mx);
+        if (amax) mmlf_amax_update_row(mx, amax, row);      // this workgroup wrote grid row `row`
+    }
+}
+
 template <int MODE, int V>
 __global__ __launch_bounds__(256) void bn_rows_kernel(const float *__restrict__ z, int cs_z,
                                                       const float *__restrict__ gy, int cs_gy, int c_off_gy,
@@ -307,13 +320,10 @@ __global__ __launch_bounds__(256) void bn_rows_kernel(const float *__restrict__ 
                                                       float *__restrict__ out, int cs_out, int c_off_out,
                                                       int C_store, int H, int W, float *__restrict__ amax, int nrows)
 {
-    // a block takes grid rows blockIdx.x, + gridDim.x, ... (launched with one block per row); a thread walks
-    // (position, channel group) pairs with stride 256 without divisions: (x, cg) += (256 / cvn, 256 % cvn) with carry.
     // Per-channel coefficients sit in LDS.  (Quarter rows per block -- 8 % faster stand-alone at 64 patches, where whole
     // rows leave a tail of blocks on an empty chip -- cost 4 ms per 60 ms step inside it: profiles/r04_ab64_bn_row_segments.log.)
     extern __shared__ float coefs[];           // [5][Cpad]: scale, shift, (mean, k1, k2, k3 for MODE 1)
-    const int P = W + GRID_PAD, R = H + GRID_PAD;
-    const int cvn = (C_store + V - 1) / V;
+    const int cvn = row_groups(C_store, V);
     const int Cpad = cvn * V;
     for (int c = threadIdx.x; c < Cpad; c += blockDim.x) {
         const bool ok = c < C;
@@ -327,22 +337,14 @@ __global__ __launch_bounds__(256) void bn_rows_kernel(const float *__restrict__ 
         }
     }
     __syncthreads();
-    const int dx = 256 / cvn, dc = 256 - dx * cvn;
-    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
-    const int y = row % R;
-    const size_t base = (size_t)row * P;
-    const bool row_in = (y >= 1 && y <= H);
-    int x = threadIdx.x / cvn, cg = threadIdx.x - x * cvn;
-    float mx = 0.f;
-    for (; x < P; x += dx, cg += dc) {
-        if (cg >= cvn) { cg -= cvn; ++x; if (x >= P) break; }
+    for_each_row_pair(cvn, H, W, nrows, amax, [&](size_t q, bool interior, int cg, float &mx) {
         float o[V];
 #pragma unroll
         for (int k = 0; k < V; ++k) o[k] = 0.f;
-        if (row_in && x >= 1 && x <= W && V * cg < C) {
+        if (interior && V * cg < C) {
             float zz[V], gg[V];
-            VecIO<V>::load_nt(z + (base + x) * cs_z + V * cg, zz);
-            if (MODE == 1) VecIO<V>::load_nt(gy + (base + x) * cs_gy + c_off_gy + V * cg, gg);
+            VecIO<V>::load_nt(z + q * cs_z + V * cg, zz);
+            if (MODE == 1) VecIO<V>::load_nt(gy + q * cs_gy + c_off_gy + V * cg, gg);
 #pragma unroll
             for (int k = 0; k < V; ++k) {
                 const int c = V * cg + k;      // channels >= C have zero coefficients -> output 0
@@ -357,7 +359,7 @@ __global__ __launch_bounds__(256) void bn_rows_kernel(const float *__restrict__ 
         }
 #pragma unroll
         for (int k = 0; k < V; ++k) mx = fmaxf(mx, fabsf(o[k]));
-        float *op = out + (base + x) * cs_out + c_off_out + V * cg;
+        float *op = out + q * cs_out + c_off_out + V * cg;
         if (V * cg + V - 1 < C_store) {
             VecIO<V>::store_nt(op, o);
         } else {
@@ -365,9 +367,7 @@ __global__ __launch_bounds__(256) void bn_rows_kernel(const float *__restrict__ 
             for (int k = 0; k < V; ++k)
                 if (V * cg + k < C_store) op[k] = o[k];
         }
-    }
-    if (amax) mmlf_amax_update_row(mx, amax, row);      // this workgroup wrote grid row `row`
-    }
+    });
 }
 
 // ReLU backward of a channel slice (model_no_batchnorm: the stream nets' last blocks write ReLU outputs straight into the
@@ -383,44 +383,32 @@ __global__ __launch_bounds__(256) void relu_slice_rows_kernel(const float *__res
                                                               float *__restrict__ dst, int cs_dst, int H, int W,
                                                               float *__restrict__ amax, int nrows)
 {
-    const int P = W + GRID_PAD, R = H + GRID_PAD;
-    const int cvn = cs_dst / V;
-    const int dx = 256 / cvn, dc = 256 - dx * cvn;
-    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
-        const int y = row % R;
-        const size_t base = (size_t)row * P;
-        const bool row_in = (y >= 1 && y <= H);
-        int x = threadIdx.x / cvn, cg = threadIdx.x - x * cvn;
-        float mx = 0.f;
-        for (; x < P; x += dx, cg += dc) {
-            if (cg >= cvn) { cg -= cvn; ++x; if (x >= P) break; }
-            float o[V];
+    for_each_row_pair(cs_dst / V, H, W, nrows, amax, [&](size_t q, bool interior, int cg, float &mx) {
+        float o[V];
 #pragma unroll
-            for (int k = 0; k < V; ++k) o[k] = 0.f;
-            if (row_in && x >= 1 && x <= W && V * cg < C) {
-                const float *sp = src + (base + x) * cs_src + c_off + V * cg;
-                const float *rp = ref + (base + x) * cs_ref + ref_off + V * cg;
-                float rr[V];
-                if (V * cg + V - 1 < C) {
-                    VecIO<V>::load_nt(sp, o);
-                    VecIO<V>::load_nt(rp, rr);
-                } else {
+        for (int k = 0; k < V; ++k) o[k] = 0.f;
+        if (interior && V * cg < C) {
+            const float *sp = src + q * cs_src + c_off + V * cg;
+            const float *rp = ref + q * cs_ref + ref_off + V * cg;
+            float rr[V];
+            if (V * cg + V - 1 < C) {
+                VecIO<V>::load_nt(sp, o);
+                VecIO<V>::load_nt(rp, rr);
+            } else {
 #pragma unroll
-                    for (int k = 0; k < V; ++k) {
-                        const bool in = V * cg + k < C;
-                        o[k] = in ? sp[k] : 0.f;
-                        rr[k] = in ? rp[k] : 0.f;
-                    }
+                for (int k = 0; k < V; ++k) {
+                    const bool in = V * cg + k < C;
+                    o[k] = in ? sp[k] : 0.f;
+                    rr[k] = in ? rp[k] : 0.f;
                 }
-#pragma unroll
-                for (int k = 0; k < V; ++k) o[k] = rr[k] > 0.f ? o[k] : 0.f;
             }
 #pragma unroll
-            for (int k = 0; k < V; ++k) mx = fmaxf(mx, fabsf(o[k]));
-            VecIO<V>::store_nt(dst + (base + x) * cs_dst + V * cg, o);
+            for (int k = 0; k < V; ++k) o[k] = rr[k] > 0.f ? o[k] : 0.f;
         }
-        if (amax) mmlf_amax_update_row(mx, amax, row);      // this workgroup wrote grid row `row`
-    }
+#pragma unroll
+        for (int k = 0; k < V; ++k) mx = fmaxf(mx, fabsf(o[k]));
+        VecIO<V>::store_nt(dst + q * cs_dst + V * cg, o);
+    });
 }
 
 // BatchNorm apply + ReLU of the four stream nets' last blocks in ONE pass over the concat buffer (torch.cat,
@@ -432,8 +420,7 @@ __global__ __launch_bounds__(256) void bn_apply4_kernel(BnApply4 s, int cs_z, in
                                                         int H, int W, float *__restrict__ amax, int nrows)
 {
     extern __shared__ float coefs[];           // [2][4 * C]: scale, shift in concat order
-    const int P = W + GRID_PAD, R = H + GRID_PAD;
-    const int C4 = 4 * C, half = C / 2, cvn = 2 * C;     // channel pairs per position row
+    const int C4 = 4 * C, half = C / 2;
     for (int c = threadIdx.x; c < C4; c += blockDim.x) {
         const int k = c / C, cl = c - k * C;
         const float *sc = k == 0 ? s.scale[0] : k == 1 ? s.scale[1] : k == 2 ? s.scale[2] : s.scale[3];
@@ -442,28 +429,19 @@ __global__ __launch_bounds__(256) void bn_apply4_kernel(BnApply4 s, int cs_z, in
         coefs[C4 + c] = sh[cl];
     }
     __syncthreads();
-    const int dx = 256 / cvn, dc = 256 - dx * cvn;
-    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
-        const int y = row % R;
-        const size_t base = (size_t)row * P;
-        const bool row_in = (y >= 1 && y <= H);
-        int x = threadIdx.x / cvn, g = threadIdx.x - x * cvn;
-        float mx = 0.f;
-        for (; x < P; x += dx, g += dc) {
-            if (g >= cvn) { g -= cvn; ++x; if (x >= P) break; }
-            float2 o = make_float2(0.f, 0.f);
-            if (row_in && x >= 1 && x <= W) {
-                const int k = g / half, cl = 2 * (g - k * half);
-                const float *zp = k == 0 ? s.z[0] : k == 1 ? s.z[1] : k == 2 ? s.z[2] : s.z[3];
-                const float2 zz = *reinterpret_cast<const float2 *>(zp + (base + x) * cs_z + cl);
-                o.x = fmaxf(fmaf(zz.x, coefs[2 * g], coefs[C4 + 2 * g]), 0.f);
-                o.y = fmaxf(fmaf(zz.y, coefs[2 * g + 1], coefs[C4 + 2 * g + 1]), 0.f);
-            }
-            mx = fmaxf(mx, fmaxf(o.x, o.y));
-            *reinterpret_cast<float2 *>(out + (base + x) * C4 + 2 * g) = o;
+    // channel pairs: 2 C per position row
+    for_each_row_pair(2 * C, H, W, nrows, amax, [&](size_t q, bool interior, int g, float &mx) {
+        float2 o = make_float2(0.f, 0.f);
+        if (interior) {
+            const int k = g / half, cl = 2 * (g - k * half);
+            const float *zp = k == 0 ? s.z[0] : k == 1 ? s.z[1] : k == 2 ? s.z[2] : s.z[3];
+            const float2 zz = *reinterpret_cast<const float2 *>(zp + q * cs_z + cl);
+            o.x = fmaxf(fmaf(zz.x, coefs[2 * g], coefs[C4 + 2 * g]), 0.f);
+            o.y = fmaxf(fmaf(zz.y, coefs[2 * g + 1], coefs[C4 + 2 * g + 1]), 0.f);
         }
-        if (amax) mmlf_amax_update_row(mx, amax, row);
-    }
+        mx = fmaxf(mx, fmaxf(o.x, o.y));
+        *reinterpret_cast<float2 *>(out + q * C4 + 2 * g) = o;
+    });
 }
 
 // (Round 4 measured a second form of these two passes -- a fixed channel group per thread with its coefficients in
@@ -471,9 +449,7 @@ __global__ __launch_bounds__(256) void bn_apply4_kernel(BnApply4 s, int cs_z, in
 // -- and persistent row grids for the form above: the same bytes per second stand-alone, 1-3 % slower inside the step;
 // DESIGN.md section 4.8, profiles/r04_bn_bench_*.log, r04_ab_bench_bn*.log; the code is in the history: commit 5c543cc.)
 
-// NCHW <-> grid
-#define PACK_XT 128   // positions per transpose tile of pack_nchw_kernel (halved until the tile fits 32 KB: wide tensors;
-                      // at 64 KB two workgroups per CU packed the 108-channel DPP gradient 0.5 ms slower)
+// NCHW <-> grid (the tiles' positions: row_walk.h)
 __global__ __launch_bounds__(256) void pack_nchw_kernel(const float *__restrict__ src, int C,
                                                         float *__restrict__ grid, int cs, int H, int W,
                                                         float *__restrict__ amax, int xt)
@@ -1082,7 +1058,7 @@ __global__ __launch_bounds__(256) void shift_pack_kernel(const float *__restrict
     }
     __syncthreads();
     const int tl = threadIdx.x & (xt - 1), c_first = threadIdx.x >> xt_log, c_step = 256 >> xt_log;
-    const int dxl = 256 / c4n, dcg = 256 - dxl * c4n;          // the write-out's (position, channel group) stride, once
+    const RowWalk wo = row_walk(c4n);                          // the write-out's (position, channel group) stride, once
     const size_t plane = (size_t)H * W;
     float mx = 0.f;
     for (int x0 = 0; x0 < P; x0 += xt) {
@@ -1117,9 +1093,8 @@ __global__ __launch_bounds__(256) void shift_pack_kernel(const float *__restrict
             if (ch >= 3) { ch -= 3; ++view; }
         }
         __syncthreads();
-        int xl = threadIdx.x / c4n, cg = threadIdx.x - xl * c4n;          // channel group fastest: coalesced grid writes
-        for (; xl < nx; xl += dxl, cg += dcg) {
-            if (cg >= c4n) { cg -= c4n; ++xl; if (xl >= nx) break; }
+        int xl, cg;                                                       // channel group fastest: coalesced grid writes
+        for (bool in = row_walk_start(wo, threadIdx.x, nx, xl, cg); in; in = row_walk_step(wo, nx, xl, cg)) {
             const float4 o = make_float4(tile[(4 * cg) * pitch + xl], tile[(4 * cg + 1) * pitch + xl],
                                          tile[(4 * cg + 2) * pitch + xl], tile[(4 * cg + 3) * pitch + xl]);
             mx = fmaxf(fmaxf(mx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
@@ -1552,9 +1527,7 @@ extern "C" int mmlf_pack_nchw(const float *nchw, int C, float *grid, int cs, int
 {
     MMLF_CHECK_ARG(nchw && grid && C > 0 && cs % 4 == 0 && C <= cs, "mmlf_pack_nchw: C=%d cs=%d", C, cs);
     MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_pack_nchw: bad shape B=%d H=%d W=%d", B, H, W);
-    int xt = PACK_XT;            // DPP with many views packs a gradient of 4*views*3 channels (132 at 11 views)
-    constexpr size_t tile_limit = 32 * 1024;
-    while (xt > 4 && (size_t)cs * (xt | 1) * sizeof(float) > tile_limit) xt >>= 1;
+    const int xt = pack_tile_positions(cs);
     const size_t lds = (size_t)cs * (xt | 1) * sizeof(float);
     MMLF_CHECK_ARG(lds <= 64 * 1024, "mmlf_pack_nchw: cs=%d does not fit the transpose tile", cs);
     hipLaunchKernelGGL(pack_nchw_kernel, dim3(B * (H + GRID_PAD)), dim3(256), lds, (hipStream_t)stream, nchw, C, grid, cs, H, W,
@@ -1647,8 +1620,7 @@ extern "C" int mmlf_unpack_nchw(const float *grid, int cs, float *nchw, int C, i
 {
     MMLF_CHECK_ARG(nchw && grid && C > 0 && C <= cs && cs % 4 == 0, "mmlf_unpack_nchw: C=%d cs=%d", C, cs);
     MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_unpack_nchw: bad shape B=%d H=%d W=%d", B, H, W);
-    int xt = 32;
-    while (xt > 1 && (size_t)xt * (C | 1) * sizeof(float) > 32 * 1024) xt >>= 1;
+    const int xt = unpack_tile_positions(C);
     hipLaunchKernelGGL(unpack_nchw_kernel, dim3(B * H), dim3(256), (size_t)xt * (C | 1) * sizeof(float), (hipStream_t)stream,
                        grid, cs, nchw, C, H, W, xt);
     return mmlf_launch_status("mmlf_unpack_nchw");
@@ -1783,9 +1755,8 @@ extern "C" int mmlf_shift_pack(const float *in, int kind, float *grid, int cs, c
     MMLF_CHECK_ARG(kind >= 0 && kind <= 3, "mmlf_shift_pack: kind=%d", kind);
     MMLF_CHECK_ARG(S > 0 && views > 0 && H > 0 && W > 0 && cs % 4 == 0 && views * 3 <= cs, "mmlf_shift_pack: S=%d views=%d cs=%d",
                    S, views, cs);
-    int xt = PACK_XT, xt_log = 7;                 // 128 positions per piece, halved until the tile fits 32 KB
-    static_assert(PACK_XT == 128, "xt_log");
-    while (xt > 4 && (size_t)cs * (xt | 1) * sizeof(float) > 32 * 1024) { xt >>= 1; --xt_log; }
+    int xt = pack_tile_positions(cs), xt_log = 0;             // the pack's pieces: a power of two, passed as its logarithm
+    while ((1 << xt_log) < xt) ++xt_log;
     const size_t lds = (size_t)cs * (xt | 1) * sizeof(float) + (size_t)views * sizeof(ShiftPackTab);
     MMLF_CHECK_ARG(lds <= 64 * 1024 && cs / 4 <= 256, "mmlf_shift_pack: cs=%d does not fit the transpose tile", cs);
     xt = xt_log;

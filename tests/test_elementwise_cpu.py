@@ -1,12 +1,19 @@
 """The BatchNorm / layout tests without a GPU: the float64 references tests/test_gpu_elementwise.py holds the kernels against
 are nn.BatchNorm2d + nn.ReLU and their gradients, the grid <-> NCHW helpers invert each other, and that file's shape lists
 reach every kernel path they exist for."""
+import functools
+import json
+import os
+import subprocess
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from tests_helpers import bn_apply_ref, bn_bwd_ref, bn_stats_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _grid(t, fill=float('nan')):
@@ -89,51 +96,35 @@ def test_grid_from_nchw_and_nchw_from_grid_invert_each_other(offset):
 
 
 # ------------------------------------------------------------------ the GPU shapes hit what they exist for
-# csrc/elementwise.hip, transcribed
-def _rows_walk(c_store):
-    """bn_rows_kernel: (cvn, dx, dc) of the thread walk (x, cg) += (dx, dc) with one carry"""
-    cvn = (c_store + 3) // 4
-    dx = 256 // cvn
-    return cvn, dx, 256 - dx * cvn
+# the walk and the tile sizes come from the kernels' own functions (csrc/row_walk.h), listed by tools/row_walk.hip
+@pytest.fixture(scope='module')
+def lister(tmp_path_factory):
+    """tools/row_walk.hip, compiled for the host: (walk(cvn, limits), sizes(n)), both cached"""
+    from mmlf_amd.csrc import build
+    if not os.path.exists(build.HIPCC):
+        pytest.skip('no hipcc')
+    exe = str(tmp_path_factory.mktemp('row_walk') / 'row_walk')
+    subprocess.run([build.HIPCC, '--offload-arch=gfx950', '-I', build.HERE, os.path.join(ROOT, 'tools', 'row_walk.hip'), '-o', exe],
+                   check=True, capture_output=True, text=True, timeout=300)
+
+    @functools.lru_cache(maxsize=None)
+    def run(*args):
+        return json.loads(subprocess.run([exe, *map(str, args)], check=True, capture_output=True, text=True, timeout=60).stdout)
+
+    def walk(cvn, limits):
+        """(cvn, dx, dc), {limit: row}: per row the 256 threads' [pairs visited, carries, left through the carry], the hits
+        of every (x, cg) and the visits outside the row"""
+        out = run('walk', cvn, *limits)
+        assert [r['limit'] for r in out['rows']] == list(limits) and all(len(r['threads']) == 256 for r in out['rows'])
+        return tuple(out['walk']), {r['limit']: r for r in out['rows']}
+
+    return walk, lambda n: run('sizes', n)
 
 
-def _walk_events(c_store, P, tid):
-    """what thread `tid` of bn_rows_kernel meets on a row of pitch P: (positions visited, carries, left through the carry)"""
-    cvn, dx, dc = _rows_walk(c_store)
-    x, cg = divmod(tid, cvn)
-    seen, carries, left = 0, 0, False
-    while x < P:
-        if cg >= cvn:
-            cg -= cvn
-            x += 1
-            carries += 1
-            if x >= P:
-                left = True
-                break
-        assert 0 <= cg < cvn
-        seen += 1
-        x += dx
-        cg += dc
-    return seen, carries, left
-
-
-def _pack_xt(cs):
-    xt = 128
-    while xt > 4 and cs * (xt | 1) * 4 > 32 * 1024:
-        xt >>= 1
-    return xt
-
-
-def _unpack_xt(C):
-    xt = 32
-    while xt > 1 and xt * (C | 1) * 4 > 32 * 1024:
-        xt >>= 1
-    return xt
-
-
-def _ppi(C):
-    cvn = (C + 3) // 4
-    return cvn, 256 // cvn
+def _covers_once(walk, cvn, limits):
+    """the walk reaches every (position, group) of a row exactly once and nothing else"""
+    for P, row in walk(cvn, tuple(limits))[1].items():
+        assert len(row['hits']) == P * cvn and set(row['hits']) == {1} and row['outside'] == 0, (cvn, P)
 
 
 def _aligned16(cs, c_off):
@@ -142,9 +133,13 @@ def _aligned16(cs, c_off):
     return cs % 4 == 0 and c_off % 4 == 0
 
 
-def test_gpu_shape_lists_reach_every_class():
+def test_gpu_shape_lists_reach_every_class(lister):
     import test_gpu_elementwise as t
     from mmlf_amd import engine
+    walk, sizes = lister
+    rows_walk = lambda c_store: walk(sizes(c_store)['groups'], ())[0]      # bn_rows_kernel: (cvn, dx, dc) at a store width
+    ppi_of = lambda C: tuple(sizes(C)['reduce'])
+    pack_xt, unpack_xt = (lambda cs: sizes(cs)['pack_xt']), (lambda C: sizes(C)['unpack_xt'])
     # the lists hold what they were given
     assert set(t.FRAMES) >= {(1, 1, 1), (1, 1, 37), (2, 29, 1), (3, 5, 29), (3, 10, 14), (2, 10, 125), (2, 10, 126), (2, 10, 127),
                              (2, 3, 30), (2, 3, 31), (2, 3, 300), (1, 2, 514)}
@@ -169,45 +164,49 @@ def test_gpu_shape_lists_reach_every_class():
 
     # ---- bn_rows_kernel: the stores of the apply (C and cs_z, the slices) and of the backward apply (cs_z)
     stores = {c for C, cs in t.CHANNELS + [t.APPLY_ONLY] for c in t._c_stores(C, cs)} | {s[3] for s in t.SLICES}
-    walks = {c: _rows_walk(c) for c in stores}
+    walks = {c: rows_walk(c) for c in stores}
     assert any(cvn == 1 for cvn, _, _ in walks.values())                    # cvn = 1
     assert {2, 8, 16} <= {cvn for cvn, _, dc in walks.values() if dc == 0}  # cvn divides 256: no carry ever
     assert walks[70] == (18, 14, 4) and walks[72] == (18, 14, 4)
-    assert _rows_walk(t.APPLY_ONLY[0])[1] == 1 and _rows_walk(t.APPLY_ONLY[1])[1] == 1      # dx = 1
+    assert rows_walk(t.APPLY_ONLY[0])[1] == 1 and rows_walk(t.APPLY_ONLY[1])[1] == 1      # dx = 1
     assert max(cvn for cvn, _, _ in walks.values()) <= 256
     assert any(c % 4 for c in stores) and any(c % 4 == 0 for c in stores)   # the scalar tail store | whole groups only
     assert any(c_store > C for C, cs in t.CHANNELS for c_store in t._c_stores(C, cs))       # pad channels written as zeros
     assert any(s[3] > s[0] for s in t.SLICES)
     assert min(pitches) == 3 and any(dx > 3 for _, dx, _ in walks.values())                 # a pitch shorter than dx
+    upitches = tuple(sorted(set(pitches)))
     for c in stores:                                                        # every walk with a carry: taken in mid-row, and
         cvn, dx, dc = walks[c]                                              # taken as the way out of the row
         if dc == 0:
             continue
-        ev = [_walk_events(c, P, tid) for P in pitches for tid in range(256)]
+        ev = [e for row in walk(cvn, upitches)[1].values() for e in row['threads']]
         assert any(carries and not left for _, carries, left in ev), c
         assert any(left for _, _, left in ev), c
         assert any(seen >= 3 for seen, _, _ in ev), c
-    # the walk as transcribed reaches every (position, group) of a row exactly once, at every store width and pitch in use
+    # the kernels' walk reaches every (position, group) of a row exactly once, at every store width and pitch in use
     for c in stores:
-        cvn = walks[c][0]
-        for P in sorted(set(pitches)):
-            hits = {}
-            for tid in range(256):
-                x, cg = divmod(tid, cvn)
-                while x < P:
-                    if cg >= cvn:
-                        cg -= cvn
-                        x += 1
-                        if x >= P:
-                            break
-                    hits[(x, cg)] = hits.get((x, cg), 0) + 1
-                    x += walks[c][1]
-                    cg += walks[c][2]
-            assert len(hits) == P * cvn and set(hits.values()) == {1}, (c, P)
+        _covers_once(walk, walks[c][0], upitches)
     # mmlf_bn_apply_relu4 walks channel PAIRS: cvn = 2 C
     for C, cs_z in t.APPLY4:
         assert C % 2 == 0 and cs_z % 2 == 0 and 8 * C * 4 <= 48 * 1024
+        _covers_once(walk, 2 * C, upitches)
     assert any(cs_z % 4 for _, cs_z in t.APPLY4) and {256 % (2 * C) == 0 for C, _ in t.APPLY4} == {True, False}
+    assert {walk(2 * C, ())[0][2] == 0 for C, _ in t.APPLY4} == {True, False}                # the pair walk with and without a carry
+    # shift_pack_kernel's write-out walks the pieces of a row, nx = min(xt, P - x0), in groups of four: cvn = cs / 4
+    import test_ensamble as te
+    for views in te.SHIFT_PACK_VIEWS:
+        cs = engine.cs_of(views * 3)
+        xt = pack_xt(cs)
+        pieces = {min(xt, W + 2 - x0) for _, W in te.SHIFT_PACK_FRAMES for x0 in range(0, W + 2, xt)}
+        _covers_once(walk, cs // 4, sorted(pieces))
+    assert set(te.SHIFT_PACK_VIEWS) >= {9, 7} and set(te.SHIFT_PACK_FRAMES) >= {(24, 24), (9, 40), (33, 17), (3, 2)}
+    sp = tuple(sorted({W + 2 for _, W in te.SHIFT_PACK_FRAMES}))            # every pitch here is one piece: below xt = 128
+    assert walk(8, ())[0] == (8, 32, 0) and pack_xt(32) == 128 and pack_xt(24) == 128 and max(sp) < 128
+    w7, rows7 = walk(6, sp)
+    assert w7 == (6, 42, 4) and 4 in rows7                                  # a carry | a pitch below dx: one pair per thread
+    assert {seen for seen, _, _ in rows7[4]['threads']} == {0, 1}
+    ev = [e for row in rows7.values() for e in row['threads']]
+    assert any(carries and not left for _, carries, left in ev) and any(left for _, _, left in ev)
 
     # ---- VecIO<4>: one 16-byte access or two 8-byte ones
     cls = {s: _aligned16(s[1], s[2]) for s in t.SLICES}
@@ -216,9 +215,9 @@ def test_gpu_shape_lists_reach_every_class():
     assert set(t.SLICE_FRAMES) <= set(t.FRAMES) and (1, 1, 1) in t.SLICE_FRAMES and len(t.SLICE_FRAMES) >= 3
 
     # ---- bn_reduce_body: positions per iteration against the row, blocks against the rows
-    ppis = {C: _ppi(C) for C, _ in t.CHANNELS}
-    assert ppis[1] == (1, 256) and ppis[512] == (128, 2) and _ppi(t.STATS_LIMIT[0]) == (256, 1)
-    assert _ppi(513)[0] > 128 and _ppi(1025)[0] > 256                       # what the wrappers refuse
+    ppis = {C: ppi_of(C) for C, _ in t.CHANNELS}
+    assert ppis[1] == (1, 256) and ppis[512] == (128, 2) and ppi_of(t.STATS_LIMIT[0]) == (256, 1)
+    assert ppi_of(513)[0] > 128 and ppi_of(1025)[0] > 256                       # what the wrappers refuse
     assert any(256 % cvn for cvn, _ in ppis.values()) and any(256 % cvn == 0 for cvn, _ in ppis.values())    # idle threads
     widths = [W for _, _, W in t.FRAMES]
     for C, (cvn, ppi) in ppis.items():
@@ -237,14 +236,14 @@ def test_gpu_shape_lists_reach_every_class():
     # ---- pack: the tile walks the PITCH; unpack: the tile walks W
     lp = [W + 2 for _, _, W in t.LAYOUT_FRAMES]
     lw = [W for _, _, W in t.LAYOUT_FRAMES]
-    xts = {cs: _pack_xt(cs) for _, cs in t.CHANNELS}
+    xts = {cs: pack_xt(cs) for _, cs in t.CHANNELS}
     assert set(xts.values()) == {128, 64, 32, 16, 8} and xts[280] == 16 and xts[8] == 128
-    assert _pack_xt(1024) == 4 and 1024 * 5 * 4 <= 64 * 1024
+    assert pack_xt(1024) == 4 and 1024 * 5 * 4 <= 64 * 1024
     for xt in set(xts.values()):
         assert any(P < xt for P in lp) and any(P % xt == 0 for P in lp) and any(P % xt == 1 and P > xt for P in lp), xt
         assert any(1 < P % xt < xt for P in lp if P > xt), xt
     assert {127, 128, 129, 32, 33} <= set(lp)
-    uxt = {C: _unpack_xt(C) for C, _ in t.CHANNELS}
+    uxt = {C: unpack_xt(C) for C, _ in t.CHANNELS}
     assert set(uxt.values()) == {32, 16, 8}
     for xt in set(uxt.values()):
         assert any(W < xt for W in lw) and any(W % xt == 0 and W >= xt for W in lw) and any(W % xt and W > xt for W in lw), xt

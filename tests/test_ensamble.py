@@ -84,9 +84,19 @@ def test_shift_hip_matches_reference():
             np.testing.assert_array_equal(outs[i][k].cpu().numpy(), g[f'shift_{d}_{i}'][0], err_msg=f'{d} {i}')
 
 
+# The write-out of shift_pack_kernel walks (position, group of four channels) pairs of a piece of the row with a carry
+# (csrc/row_walk.h).  9 views: cs = 32, 8 groups, 256 % 8 = 0 -- never a carry.  7 views: cs = 24, 6 groups, the walk moves on
+# by (42, 4): at a pitch of 4 (frame (3, 2)) a thread is out of the row on its first step; at a pitch of 45 (frame (2, 43))
+# threads carry in mid-row (x = 0 -> 43) and leave through the carry (x = 2 -> 44 -> 45).  tests/test_elementwise_cpu.py holds
+# these lists to that.
+SHIFT_PACK_VIEWS = (9, 7)
+SHIFT_PACK_FRAMES = [(24, 24), (9, 40), (33, 17), (3, 2), (2, 43)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('shape', [(24, 24), (9, 40), (33, 17)])
-def test_shift_pack_writes_the_same_bits_as_shift_then_pack(shape):
+@pytest.mark.parametrize('views', SHIFT_PACK_VIEWS)
+@pytest.mark.parametrize('shape', SHIFT_PACK_FRAMES)
+def test_shift_pack_writes_the_same_bits_as_shift_then_pack(shape, views):
     """mmlf_shift_pack (round 6: the Ensamble's members sheared straight into the trunk's grid layout) against
     mmlf_shift_views followed by mmlf_pack_nchw, per stream kind: the same grid bytes (borders, pad channels and slack
     included) and the same amax array; the shifts are the golden's (hci4d.py:907-990 is pinned by test_shift_hip_matches_reference)."""
@@ -94,7 +104,6 @@ def test_shift_pack_writes_the_same_bits_as_shift_then_pack(shape):
     from mmlf_amd._lib import call, ptr
     dev = torch.device('cuda:0')
     H, W = shape
-    views = 9
     gen = torch.Generator().manual_seed(H * 100 + W)
     src = [torch.rand((views, 3, H, W), generator=gen).to(dev) for _ in range(4)]
     disps = list(DISPS) + [float(W) + 0.5, -float(H) - 1.25]                 # incl. |shift| >= size: the roll's identity clamp
