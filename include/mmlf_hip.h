@@ -163,7 +163,9 @@ int mmlf_conv2x2_blocks(int K, int N, int B, int H, int W);
  * FMAs straight from the OIHW master filter (no packing, no operand split, any MMLF_CONV_MODE).  Same semantics as
  * mmlf_conv2x2 for the written extent: every position of the output grid is written (zeros outside the valid
  * extent and in the pad channels), the output's amax array is raised.  workspace:
- * mmlf_conv2x2_thin_workspace_floats(B,H,W) floats; the weight gradient's: mmlf_conv2x2_wgrad_thin_workspace_floats(Cin). */
+ * mmlf_conv2x2_thin_workspace_floats(B,H,W) floats; the weight gradient's: mmlf_conv2x2_wgrad_thin_workspace_floats(Cin).
+ * mmlf_conv2x2_wgrad_thin with gw_oihw == NULL (and gb != NULL): the bias gradient alone, as in mmlf_conv2x2_wgrad
+ * (cs_g % 4 == 0 then). */
 int64_t mmlf_conv2x2_thin_workspace_floats(int B, int H, int W);
 int mmlf_conv2x2_thin(const float *in, int cs_in, int K, const float *w_oihw, const float *bias, int N,
                       float *out, int cs_out, int out_shift, int vh, int vw, int B, int H, int W, int relu,
@@ -176,12 +178,17 @@ int mmlf_conv2x2_wgrad_thin(const float *in, int cs_in, int Cin, const float *g,
 /* Weight + bias gradient of the convolution above (autograd of feed_forward.py:123,125 reached
  * from train/cli.py:257):  gw[co][ci][tap] (+)= sum_q in[q + off_t][ci] * g[q + g_shift][co],
  * gb[co] (+)= sum_q g[q + g_shift][co].  g must be zero outside its stored extent.
- * variant maps taps back to the OIHW master; accumulate != 0 adds into gw/gb (shared stream nets). */
+ * variant maps taps back to the OIHW master; accumulate != 0 adds into gw/gb (shared stream nets).
+ * gb == NULL: the weight gradient alone.  gw_oihw == NULL (with gb != NULL): the bias gradient alone -- one pass over g
+ * (`in` is not read), for Cout <= 512 and cs_g % 4 == 0: float64 partial sums per workgroup in `workspace`, summed in a fixed
+ * order and rounded once (accumulate joins before the rounding; no atomics, two launches give the same bits).  Both NULL is
+ * an error and launches nothing. */
 int mmlf_conv2x2_wgrad(const float *in, int cs_in, int Cin, const float *g, int cs_g, int Cout,
                        int g_shift, float *gw_oihw, float *gb, int variant, int accumulate,
                        float *workspace, int B, int H, int W, void *stream);
 
-/* split-precision variant of mmlf_conv2x2_wgrad (same arguments; see mmlf_conv2x2_split) */
+/* split-precision variant of mmlf_conv2x2_wgrad (same arguments; see mmlf_conv2x2_split).  gw_oihw == NULL (with
+ * gb != NULL): the bias gradient alone, as there. */
 int mmlf_conv2x2_wgrad_split(const float *in, int cs_in, int Cin, const float *g, int cs_g, int Cout,
                              int g_shift, float *gw_oihw, float *gb, int variant, int accumulate,
                              float *workspace, int B, int H, int W, void *stream);
@@ -191,7 +198,8 @@ int mmlf_conv2x2_wgrad_split(const float *in, int cs_in, int Cin, const float *g
  * scales (the tensors' global ones), split between the two operands per chunk by the maxima of the grid rows it
  * reads: in * (sA * 2^x), g * (sG * 2^-x), x = half the difference of the operands' headroom.  A chunk keeps all
  * 22 bits of both operands while its products are within 2^-36 of the launch's largest (smaller ones are below
- * float32's own accumulation error of the sum). */
+ * float32's own accumulation error of the sum).  gw_oihw == NULL (with gb != NULL): the bias gradient alone, as in
+ * mmlf_conv2x2_wgrad (the amax arrays are still required and not read). */
 int mmlf_conv2x2_wgrad_h2(const float *in, int cs_in, int Cin, const float *g, int cs_g, int Cout,
                           int g_shift, float *gw_oihw, float *gb, int variant, int accumulate,
                           float *workspace, int B, int H, int W, const float *in_amax, const float *g_amax,
@@ -301,7 +309,8 @@ int mmlf_conv3x3(const float *in, int cs_in, int K, const float *packed, const f
                  void *stream);
 /* weight + bias gradient:  gw[co][ci][sy][sx] (+)= sum_q in[q + dy*P + dx][ci] * g[q + P + 1][co] with (sy, sx) the master
  * tap of packed tap (dy, dx) under `variant`, gb[co] (+)= sum_q g[q + P + 1][co] (gb nullable); g zero outside its extent.
- * workspace: mmlf_wgrad3x3_workspace_floats(Cin, Cout, B, H, W) floats. */
+ * workspace: mmlf_wgrad3x3_workspace_floats(Cin, Cout, B, H, W) floats.  gw_oihw == NULL (with gb != NULL): the bias
+ * gradient alone, as in mmlf_conv2x2_wgrad; both NULL is an error. */
 int64_t mmlf_wgrad3x3_workspace_floats(int Cin, int Cout, int B, int H, int W);
 int mmlf_conv3x3_wgrad(const float *in, int cs_in, int Cin, const float *g, int cs_g, int Cout, float *gw_oihw, float *gb,
                        int variant, int accumulate, float *workspace, int B, int H, int W, void *stream);

@@ -5,6 +5,7 @@
 // mmlf/model/feed_forward.py:123,125 under autograd (mmlf/train/cli.py:257).
 #include "conv_device.h"
 #include "wgrad_map.h"
+#include "row_walk.h"
 
 #ifdef MMLF_BOUNDS_DEBUG
 int mmlf_oob_counts_wgrad(unsigned long long *host8, int reset)
@@ -825,6 +826,102 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wave_kernel(const float *__r
 }
 
 // ---------------------------------------------------------------------------------------------
+// The bias gradient WITHOUT a weight gradient (gw == NULL at an entry point: the layer's filter is frozen, its bias trains):
+// gb[c] (+)= sum_q g[q + g_shift][c] over the padded grid.  g is zero outside its extent (the entry points' contract), so no
+// mask is read: one pass over g and nothing else, 4 NQ cs_g bytes, HBM-bound.  A row kernel (row_walk.h): a block takes
+// grid rows blockIdx.x, + gridDim.x, ...; a thread keeps ONE group of four channels (reduce_walk) and meets positions
+// pl, pl + ppi, ... < P of each row with a 16-byte non-temporal load, so every read is at the float index
+//     ((row * P + x + g_shift) * cs_g + 4 * cg + k,   row < B * R,  x < P,  4 * cg + k < cs_g  (4 cvn <= cs_g: cs_g % 4 == 0)
+// below (NQ + g_shift) * cs_g, inside what mmlf_audit_wgrad_h2 / mmlf_audit_wgrad3x3 report for g.  Sums in float64; a
+// block's go to partial[blockIdx.x][C] in the entry point's workspace, and bias_grad_finish_kernel adds the blocks in a
+// fixed order and rounds once.  No atomics: two launches give the same bits.
+// ---------------------------------------------------------------------------------------------
+constexpr int BIAS_GRAD_MAX_C = 512, BIAS_GRAD_MAX_BLOCKS = 1024;
+
+__device__ __forceinline__ void bias_grad_load(const float *p, float *o, bool is_aligned)
+{
+    if (is_aligned) {                                   // streamed once: non-temporal, as bn_rows_kernel reads
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        const f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(p));
+        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = __builtin_nontemporal_load(p + k);
+    }
+}
+
+__global__ __launch_bounds__(256) void bias_grad_rows_kernel(const float *__restrict__ g, int cs_g, int C, int g_shift, int P,
+                                                             int nrows, double *__restrict__ partial)
+{
+    int cvn, ppi;                               // channel groups that hold real channels, positions per iteration
+    reduce_walk(C, 4, cvn, ppi);
+    const int tid = threadIdx.x;
+    const int pl = tid / cvn, cg = tid - pl * cvn;
+    const bool active = pl < ppi;
+    double s[4] = {0, 0, 0, 0};
+    // every access of the launch is 16-byte aligned (cs_g % 4 == 0), or none is promised to be
+    const bool aligned = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
+        const float *rp = g + ((size_t)row * P + g_shift) * cs_g + 4 * cg;
+        // two positions per iteration, both loads issued before either sum (the order of the sums stays x, x + ppi, ...)
+        for (int x = pl; active && x < P; x += 2 * ppi) {
+            float a[4], b[4] = {0.f, 0.f, 0.f, 0.f};
+            bias_grad_load(rp + (size_t)x * cs_g, a, aligned);
+            if (x + ppi < P) bias_grad_load(rp + (size_t)(x + ppi) * cs_g, b, aligned);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] += a[e];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] += b[e];
+        }
+    }
+    __shared__ double red[ROW_THREADS][4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) red[tid][e] = s[e];
+    __syncthreads();
+    if (tid < cvn) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            double acc = 0;
+            for (int p = 0; p < ppi; ++p) acc += red[p * cvn + tid][e];
+            const int c = 4 * tid + e;
+            if (c < C) partial[(size_t)blockIdx.x * C + c] = acc;
+        }
+    }
+}
+
+// second stage: one wave per channel, lanes stride over the blocks' partial sums, a fixed-order shuffle tree, then ONE rounding
+// -- with the old value joined in float64 before it where the launch accumulates
+__global__ __launch_bounds__(64) void bias_grad_finish_kernel(const double *__restrict__ partial, int nblocks, int C,
+                                                              float *__restrict__ gb, int accumulate)
+{
+    const int c = blockIdx.x;
+    double acc = 0;
+    for (int blk = threadIdx.x; blk < nblocks; blk += 64) acc += partial[(size_t)blk * C + c];
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if (threadIdx.x != 0) return;
+    gb[c] = (float)(accumulate ? acc + (double)gb[c] : acc);
+}
+
+// The host side of every weight-gradient entry point called with gw == NULL (the entry point has validated its own
+// arguments).  ws_floats: the partial-sum floats that entry point's workspace query promises; the block count follows from it.
+static int bias_grad_only(const char *who, const float *g, int cs_g, int C, int g_shift, float *gb, int accumulate,
+                          float *workspace, int64_t ws_floats, const Grid &gr, hipStream_t st)
+{
+    MMLF_CHECK_ARG(C >= 1 && C <= BIAS_GRAD_MAX_C && C <= cs_g && cs_g % 4 == 0, "%s: bias gradient alone: C=%d cs_g=%d", who, C, cs_g);
+    MMLF_CHECK_ARG(gr.NQ + 2 * gr.P + 64 < (1ll << 31), "%s: batch x image too large", who);
+    // float64 partials in a float workspace: start at the first 8-byte boundary (at most one float on)
+    double *partial = reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(workspace) + 7) & ~(uintptr_t)7);
+    const int64_t room = (ws_floats - 1) / 2 / C;                  // blocks whose C doubles fit
+    MMLF_CHECK_ARG(room >= 1, "%s: bias gradient alone: the workspace holds %lld floats", who, (long long)ws_floats);
+    const int nrows = gr.B * gr.R;
+    int nblocks = nrows < BIAS_GRAD_MAX_BLOCKS ? nrows : BIAS_GRAD_MAX_BLOCKS;
+    if (nblocks > room) nblocks = (int)room;
+    hipLaunchKernelGGL(bias_grad_rows_kernel, dim3(nblocks), dim3(ROW_THREADS), 0, st, g, cs_g, C, g_shift, gr.P, nrows, partial);
+    hipLaunchKernelGGL(bias_grad_finish_kernel, dim3(C), dim3(64), 0, st, partial, nblocks, C, gb, accumulate);
+    return mmlf_launch_status(who);
+}
+
+// ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
 static int wgrad_nsplit(int nslice)
@@ -1081,7 +1178,7 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
                       float *gw, float *gb, int variant, int accumulate, float *workspace, int B, int H, int W,
                       void *stream, int planes, const float *in_amax, const float *g_amax)
 {
-    MMLF_CHECK_ARG(in && g && gw && workspace, "mmlf_conv2x2_wgrad: null pointer");
+    MMLF_CHECK_ARG(in && g && (gw || gb) && workspace, "mmlf_conv2x2_wgrad: null pointer");
     MMLF_CHECK_ARG(cs_in % 4 == 0 && cs_g % 4 == 0, "mmlf_conv2x2_wgrad: strides must be multiples of 4");
     MMLF_CHECK_ARG(Cin > 0 && Cin <= cs_in && Cout > 0 && Cout <= cs_g, "mmlf_conv2x2_wgrad: channels vs strides");
     MMLF_CHECK_ARG(Cout <= WGRAD_MAX_COUT_WIDE, "mmlf_conv2x2_wgrad: Cout=%d not supported (max %d)", Cout, WGRAD_MAX_COUT_WIDE);
@@ -1093,6 +1190,8 @@ static int wgrad_impl(const float *in, int cs_in, int Cin, const float *g, int c
     WgradArgs a = wgrad_args(in, cs_in, Cin, g, cs_g, g_shift, workspace, gr, grid_alloc_positions(gr), p.scales_off);
     a.in_amax = in_amax; a.g_amax = g_amax;
     hipStream_t st = (hipStream_t)stream;
+    if (!gw)                    // the bias gradient alone: one pass over g, partial sums where the weight gradient keeps its own
+        return bias_grad_only("mmlf_conv2x2_wgrad", g, cs_g, Cout, g_shift, gb, accumulate, workspace, p.scales_off, gr, st);
     if (planes == 2) {          // per-chunk operand scales, behind the partial sums in the workspace
         MMLF_CHECK_ARG(gr.NQpad + 2 * gr.P + 64 < (1ll << 31), "mmlf_conv2x2_wgrad_h2: batch x image too large");
         ChunkScaleArgs ca;
@@ -1206,7 +1305,7 @@ extern "C" int mmlf_conv2x2_wgrad_thin(const float *in, int cs_in, int Cin, cons
                                        float *gw_oihw, float *gb, int variant, int accumulate, float *workspace, int B,
                                        int H, int W, void *stream)
 {
-    MMLF_CHECK_ARG(in && g && gw_oihw && workspace, "mmlf_conv2x2_wgrad_thin: null pointer");
+    MMLF_CHECK_ARG(in && g && (gw_oihw || gb) && workspace, "mmlf_conv2x2_wgrad_thin: null pointer");
     MMLF_CHECK_ARG(Cout >= 1 && Cout <= THIN_MAXN && Cout <= cs_g && Cin >= 1 && Cin <= cs_in && cs_in % 4 == 0 && cs_in <= 512,
                    "mmlf_conv2x2_wgrad_thin: Cin=%d Cout=%d cs_in=%d", Cin, Cout, cs_in);
     MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0 && variant >= 0 && variant <= 2, "mmlf_conv2x2_wgrad_thin: bad shape");
@@ -1216,6 +1315,9 @@ extern "C" int mmlf_conv2x2_wgrad_thin(const float *in, int cs_in, int Cin, cons
     a.in = in; a.g = g; a.wpart = workspace; a.NQ = gr.NQ; a.npos = gr.NQ + gr.P + 2;
     a.cs_in = cs_in; a.C = Cin; a.N = Cout; a.cs_g = cs_g; a.g_shift = g_shift; a.P = gr.P; a.CIP = Cin + 1;
     hipStream_t st = (hipStream_t)stream;
+    if (!gw_oihw)
+        return bias_grad_only("mmlf_conv2x2_wgrad_thin", g, cs_g, Cout, g_shift, gb, accumulate, workspace,
+                              mmlf_conv2x2_wgrad_thin_workspace_floats(Cin), gr, st);
     const int nwaves = thin_wgrad_waves();
     hipLaunchKernelGGL(thin_wgrad_kernel, dim3(nwaves / 4), dim3(256), 0, st, a);
     const int total = 4 * (Cin + 1) * Cout;
@@ -1263,7 +1365,7 @@ extern "C" int64_t mmlf_wgrad3x3_workspace_floats(int Cin, int Cout, int B, int 
 extern "C" int mmlf_conv3x3_wgrad(const float *in, int cs_in, int Cin, const float *g, int cs_g, int Cout, float *gw_oihw,
                                   float *gb, int variant, int accumulate, float *workspace, int B, int H, int W, void *stream)
 {
-    MMLF_CHECK_ARG(in && g && gw_oihw && workspace, "mmlf_conv3x3_wgrad: null pointer");
+    MMLF_CHECK_ARG(in && g && (gw_oihw || gb) && workspace, "mmlf_conv3x3_wgrad: null pointer");
     MMLF_CHECK_ARG(B > 0 && H > 0 && W > 0, "mmlf_conv3x3_wgrad: bad shape B=%d H=%d W=%d", B, H, W);
     MMLF_CHECK_ARG(cs_in % 4 == 0 && cs_g % 4 == 0, "mmlf_conv3x3_wgrad: strides must be multiples of 4");
     MMLF_CHECK_ARG(Cin > 0 && Cin <= cs_in && Cout > 0 && Cout <= cs_g, "mmlf_conv3x3_wgrad: channels vs strides");
@@ -1272,6 +1374,9 @@ extern "C" int mmlf_conv3x3_wgrad(const float *in, int cs_in, int Cin, const flo
     MMLF_CHECK_ARG(wgrad9_plan(Cin, Cout, k), "mmlf_conv3x3_wgrad: Cout=%d not supported", Cout);
     const Grid gr = make_grid(B, H, W);
     MMLF_CHECK_ARG(gr.NQpad + 2 * gr.P + 64 < (1ll << 31), "mmlf_conv3x3_wgrad: batch x image too large");
+    if (!gw_oihw)
+        return bias_grad_only("mmlf_conv3x3_wgrad", g, cs_g, Cout, gr.P + 1, gb, accumulate, workspace, k.part_floats, gr,
+                              (hipStream_t)stream);
     WgradArgs a = wgrad_args(in, cs_in, Cin, g, cs_g, gr.P + 1, workspace, gr, grid_alloc_positions_k3(gr), k.part_floats);
     return wgrad_run_block<3>(a, k, 0, gw_oihw, gb, Cin, variant, accumulate, (hipStream_t)stream);
 }

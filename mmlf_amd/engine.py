@@ -326,7 +326,8 @@ THIN_MAX_N, THIN_MIN_K = 2, 64     # mmlf_conv2x2_thin: at most 2 output channel
 
 def wgrad(geo, x, cs_in, cin, g, cs_g, cout, g_shift, gw, gb, variant, workspace, side=False):
     """weight + bias gradient, accumulated into gw / gb (side: the launch goes to the side stream and must not share
-    scratch with main-stream launches)"""
+    scratch with main-stream launches).  gw None: the bias gradient alone, one pass over g (the entry points' bias-only
+    form; x is not read); gb None: the weight gradient alone."""
     if cout <= THIN_MAX_N and cin >= THIN_MIN_K and cs_in <= 512:
         # a matrix-vector product (the BASE / UPR head): plain float32 FMAs, bound by reading x once
         ws = _Workspace.get(x.device).scratch('thin_wgrad_side' if side else 'thin_wgrad', int(_lib.load().mmlf_conv2x2_wgrad_thin_workspace_floats(cin)))
@@ -335,7 +336,7 @@ def wgrad(geo, x, cs_in, cin, g, cs_g, cout, g_shift, gw, gb, variant, workspace
         return
     args = (ptr(x), cs_in, cin, ptr(g), cs_g, cout, g_shift, ptr(gw), ptr(gb), variant, 1, ptr(workspace),
             geo.B, geo.H, geo.W)
-    prof = PROFILE is not None and cin >= 256 and cout >= 256
+    prof = PROFILE is not None and cin >= 256 and cout >= 256 and gw is not None
     if prof:
         events = _tic()
     if CONV_MODE == 'f16x3':
@@ -422,7 +423,7 @@ def conv3(geo, x, cs_in, K, packed, bias, N, out, cs_out, relu, ref=None, cs_ref
 
 
 def wgrad3(geo, x, cs_in, cin, g, cs_g, cout, gw, gb, variant, workspace):
-    """3x3 weight + bias gradient, accumulated into gw / gb"""
+    """3x3 weight + bias gradient, accumulated into gw / gb (gw None: the bias gradient alone, as in wgrad)"""
     if CHECK_EXTENTS:
         _audit('mmlf_audit_wgrad3x3', (cs_in, cin, cs_g, cout, geo.B, geo.H, geo.W), 5,
                f'wgrad3x3 {cin}->{cout} B={geo.B} {geo.H}x{geo.W}',
@@ -455,6 +456,68 @@ class _Rec:
         self.scale = self.shift = self.smean = self.sinv = None
         self.eval = False
         self.bn, self.pk2d = spec.bn, None
+
+
+class BlockPlan:
+    """The backward launches of one live block, in backward order (Trunk.plan).  want: the wanted
+    parameters of the block, as suffixes ('0.weight', '0.bias', '2.weight', '2.bias', '3.weight', '3.bias').
+    reduce / apply: mmlf_bn_bwd_reduce / mmlf_bn_bwd_apply; wgrad2 / wgrad1: the weight-gradient launch of conv2 / conv1 (the
+    bias gradient alone where the filter itself is not wanted: gw = NULL); dgrad2 / dgrad1: the data gradient of conv2 (-> dy)
+    / conv1 (-> dx)."""
+    LAUNCHES = ('reduce', 'apply', 'wgrad2', 'dgrad2', 'wgrad1', 'dgrad1')
+    __slots__ = ('prefix', 'want') + LAUNCHES
+
+    def __init__(self, prefix, want, bn, train, need_dx):
+        self.prefix, self.want = prefix, frozenset(want)
+        want_bn = bn and bool(self.want & {'3.weight', '3.bias'})
+        self.wgrad1 = bool(self.want & {'0.weight', '0.bias'})
+        self.wgrad2 = bool(self.want & {'2.weight', '2.bias'})
+        self.dgrad1 = bool(need_dx)
+        self.dgrad2 = self.wgrad1 or self.dgrad1                    # dy
+        need_dz = self.wgrad2 or self.dgrad2
+        self.apply = bool(bn) and need_dz
+        # the batch sums feed dgamma / dbeta and, where the statistics were the batch's, the coefficients of dz
+        self.reduce = bool(bn) and (want_bn or (need_dz and bool(train)))
+
+    def launches(self):
+        return [k for k in self.LAUNCHES if getattr(self, k)]
+
+    def __eq__(self, other):
+        return isinstance(other, BlockPlan) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __repr__(self):
+        return f'BlockPlan({self.prefix}: {" ".join(self.launches())}; {sorted(self.want)})'
+
+
+class Plan:
+    """Which backward launches a step runs (Trunk.plan): a value, computed on the host without a library call.
+    trainable: the wanted parameter names; input_grads: four bools; fold: BatchNorm is folded into conv2 (blocks below the
+    head are ReLU-only ones); streams[s][k] / out[k]: the BlockPlan of a live block, None for a block that launches nothing;
+    slices[s]: stream s's mmlf_relu_bwd_slice runs (ReLU-only blocks of a live stream)."""
+
+    def __init__(self, trainable, input_grads, train, fold, streams, out, relu_only):
+        self.trainable, self.input_grads, self.train, self.fold = trainable, input_grads, train, fold
+        self.streams, self.out = streams, out
+        self.stream_live = [any(b is not None for b in blocks) for blocks in streams]
+        self.slices = [relu_only and live for live in self.stream_live]
+
+    def blocks(self):
+        """the live blocks in backward order"""
+        return ([b for b in reversed(self.out) if b is not None]
+                + [b for s in reversed(range(4)) for b in reversed(self.streams[s]) if b is not None])
+
+    def counts(self):
+        """launches of the backward pass by kind: {'wgrad', 'reduce', 'apply', 'dgrad', 'slice', 'bias_only'}; bias_only: the
+        weight-gradient launches among 'wgrad' that form a bias gradient alone"""
+        live = self.blocks()
+        n = {'wgrad': sum(b.wgrad1 + b.wgrad2 for b in live), 'reduce': sum(b.reduce for b in live),
+             'apply': sum(b.apply for b in live), 'dgrad': sum(b.dgrad1 + b.dgrad2 for b in live), 'slice': sum(self.slices)}
+        n['bias_only'] = sum((b.wgrad1 and '0.weight' not in b.want) + (b.wgrad2 and '2.weight' not in b.want) for b in live)
+        return n
+
+    def __eq__(self, other):
+        return (isinstance(other, Plan) and (self.trainable, self.input_grads, self.train, self.fold, self.streams, self.out)
+                == (other.trainable, other.input_grads, other.train, other.fold, other.streams, other.out))
 
 
 class Trunk:
@@ -502,6 +565,7 @@ class Trunk:
             self._numel.update({f'{spec.prefix}.{k}': v for k, v in n.items()})
         self._grad_names = [n for n in self._numel if n.endswith(('.weight', '.bias'))]     # what backward accumulates into
         self._checked = {}
+        self._plans = {}
 
     def _check_dict(self, what, d, names, dev):
         """every d[name]: present, on `dev`, contiguous, float32 (the BatchNorm counter int64), of the element count its block
@@ -520,12 +584,55 @@ class Trunk:
         pointer, so a channels_last model is refused, like one on another device"""
         self._check_dict('parameters', p, self._numel, dev)
 
+    # ------------------------------------------------------------------ the plan of a backward pass
+    def plan(self, trainable=None, input_grads=None, train=True, fold=None):
+        """Which backward launches run when the gradients of the parameters `trainable` (state_dict names; None: all of
+        _grad_names) and of the stacks `input_grads` (four bools; None: none) are asked for.  Both passes follow it and
+        nothing else decides a launch: forward keeps a record for the live blocks only, backward runs the listed launches.
+        A block is live if the gradient must reach its output: it has a wanted parameter, or a block beneath it in its chain
+        has one (the stream blocks are beneath out_net.0; H and V share in_net_hv's names, I and D in_net_id's), or, in a
+        stream, its stack's gradient is wanted.  train: BatchNorm's statistics are the batch's.  fold: BatchNorm is folded
+        into conv2; None: as forward decides under a tape (a 2x2 trunk in eval mode of which no parameter is wanted)."""
+        names = set(self._grad_names)
+        wanted = frozenset(names if trainable is None else trainable)
+        if not wanted <= names:
+            raise ValueError(f'Trunk.plan: {sorted(wanted - names)[0]!r} is no parameter of this trunk')
+        want_x = tuple(bool(w) for w in input_grads) if input_grads is not None else (False,) * 4
+        if len(want_x) != 4:
+            raise ValueError('Trunk.plan: input_grads takes four bools (streams H, V, I, D)')
+        if fold is None:
+            fold = self.batchnorm and not train and not wanted and self.ksize == 2
+        if fold and wanted:
+            raise ValueError('Trunk.plan: a folded BatchNorm has no parameter gradients')
+        key = (wanted, want_x, bool(train), bool(fold))
+        cached = self._plans.get(key)                # (a training run asks for the same plan twice per step)
+        if cached is not None:
+            return cached
+        if len(self._plans) >= 64:
+            self._plans.clear()
+
+        def chain(blocks, below, x_wanted):
+            """below: something beneath the chain is live (its first block's dx is needed); x_wanted: the chain's input
+            gradient itself is"""
+            out, live = [], below or x_wanted
+            for k, spec in enumerate(blocks):
+                want = {n[len(spec.prefix) + 1:] for n in wanted if n.startswith(spec.prefix + '.')}
+                need_dx = live                       # the block beneath is live, or the stack's gradient is wanted
+                live = live or bool(want)
+                out.append(BlockPlan(spec.prefix, want, spec.bn is True and not fold, train, need_dx) if live else None)
+            return out
+
+        streams = [chain(blocks, False, want_x[s]) for s, (_, _, blocks) in enumerate(self.streams)]
+        out = chain(self.out_blocks, any(b is not None for blocks in streams for b in blocks), False)
+        made = self._plans[key] = Plan(wanted, want_x, bool(train), bool(fold), streams, out, not self.batchnorm or bool(fold))
+        return made
+
     # ------------------------------------------------------------------ filters
-    def _prepack(self, p, dev, with_dgrad, input_grads=None, fold=False):
-        """every packed filter a step needs -- forward and, with_dgrad, data-gradient forms -- from ONE launch (f16 split
-        only; the other modes pack per layer).  input_grads: per stream, whether backward will form the gradient of the
-        stream's input (the data-gradient form of its first filter).  fold: BatchNorm is folded into conv2 (_block_fwd packs
-        the folded filter itself), so conv2's master filter is not packed.  Keys: (parameter name, variant, dgrad)."""
+    def _prepack(self, p, dev, plan, fold=False):
+        """every packed filter a step needs -- forward and the data-gradient forms of the launches `plan` contains (None: no
+        backward follows) -- from ONE launch (f16 split only; the other modes pack per layer).  fold: BatchNorm is folded
+        into conv2 (_block_fwd packs the folded filter itself), so conv2's master filter is not packed.
+        Keys: (parameter name, variant, dgrad)."""
         if CONV_MODE != 'f16x3' or dev.type != 'cuda' or self.ksize != 2:
             return {}
         items = []
@@ -533,24 +640,24 @@ class Trunk:
         def add(name, var, dgrad):
             items.append(((name, var, dgrad), p[name], var, dgrad))
 
-        def block(spec, var, need_dx):
+        def block(spec, var, bp):
             thin = spec.cout <= THIN_MAX_N and spec.cin >= THIN_MIN_K      # the head's first conv runs from the master filter
             own2 = not (fold and spec.bn is True)
             if not thin:
                 add(f'{spec.prefix}.0.weight', var, False)
             if own2:
                 add(f'{spec.prefix}.2.weight', var, False)
-            if with_dgrad:
-                if own2:
+            if bp is not None:
+                if own2 and bp.dgrad2:
                     add(f'{spec.prefix}.2.weight', var, True)
-                if need_dx:
+                if bp.dgrad1:
                     add(f'{spec.prefix}.0.weight', var, True)
 
         for s, (_, var, blocks) in enumerate(self.streams):
             for k, spec in enumerate(blocks):
-                block(spec, var, k > 0 or bool(input_grads and input_grads[s]))
-        for spec in self.out_blocks:
-            block(spec, VAR_IDENTITY, True)
+                block(spec, var, plan.streams[s][k] if plan else None)
+        for k, spec in enumerate(self.out_blocks):
+            block(spec, VAR_IDENTITY, plan.out[k] if plan else None)
         return _Workspace.get(dev).packed_filters(items)
 
     def _pack(self, w, var, dgrad):
@@ -691,7 +798,7 @@ class Trunk:
             rec.scale, rec.shift, rec.smean, rec.sinv = scale, shift, smean, sinv
         return out, cs_out, None
 
-    def forward(self, p, stacks, train, save, packed=None, input_grads=None, frozen=False):
+    def forward(self, p, stacks, train, save, packed=None, input_grads=None, frozen=False, trainable=None):
         """stacks: four (B, views, 3, H, W) contiguous float32 device tensors.  They, the grid tensors of `packed` and every
         entry of `p` the blocks read are validated here (_lib.check), ahead of the first call into the library.
         packed (instead of stacks): (Geometry, [four grid tensors of channel stride cs_of(3 views), with their amax arrays]) --
@@ -701,6 +808,10 @@ class Trunk:
         frozen (with save): backward will be called with grads=None (no parameter wants a gradient).  In eval mode a 2x2 trunk
         with BatchNorm then runs the inference launches (BatchNorm folded into conv2) and keeps what a model_no_batchnorm
         forward keeps: the same output bits as without a tape, and a backward without any BatchNorm launch.
+        trainable (with save): the parameter names whose gradient backward will be asked for (None: all; frozen=True means
+        the empty set).  Together with input_grads it makes the step's plan (Trunk.plan): blocks that are not live leave no
+        record and write no ReLU bits, the concat buffer is kept only for a live stream, and only the planned data gradients'
+        filter forms are packed.  BatchNorm's running statistics move in train mode whatever is frozen, as in torch.
         Returns (output NCHW (B,oc,H,W), tape or None)."""
         cin0 = self.views * 3
         if packed is not None:
@@ -725,11 +836,19 @@ class Trunk:
         _Workspace.get(dev).enter_stream()
         # BatchNorm folded into conv2: inference, and the frozen evaluation that is differentiated in its inputs (3x3 trunks
         # have no ReLU-only backward and keep the unfolded form under a tape)
-        fold = self.batchnorm and not train and (not save or (bool(frozen) and self.ksize == 2))
+        if frozen:
+            trainable = ()
+        plan = self.plan(trainable, input_grads, train) if save else None
+        fold = self.batchnorm and not train and (not save or plan.fold)
         relu_only = not self.batchnorm or fold                  # every block below the head ends in conv2's own ReLU
-        packs = self._prepack(p, dev, save, input_grads, fold)
+        packs = self._prepack(p, dev, plan, fold)
         tracked = []                  # BatchNorm counters of this pass: ONE increment launch at its end
-        tape = {'geo': geo, 'device': dev, 'streams': [], 'out': [], 'packs': packs}
+        tape = {'geo': geo, 'device': dev, 'streams': [], 'out': [], 'packs': packs, 'plan': plan}
+
+        def rec_of(live, recs):
+            """where a block leaves its record: a one-entry list for a live block, whose record (or None) joins `recs`"""
+            slot = [] if live else None
+            return slot, lambda: recs.append(slot[0] if slot else None)
         if packed is not None:
             concat, xs = geo.buf(4 * self.chs, dev), list(xs_in)
         else:
@@ -747,9 +866,11 @@ class Trunk:
             x_relu, xmask = False, None
             for k, spec in enumerate(blocks):
                 last = k == len(blocks) - 1
-                x, cs_x, xmask = self._block_fwd(geo, spec, var, x, cs_x, x_relu, xmask, p, train, recs if save else None,
+                slot, keep = rec_of(save and plan.streams[s][k] is not None, recs)
+                x, cs_x, xmask = self._block_fwd(geo, spec, var, x, cs_x, x_relu, xmask, p, train, slot,
                                                  out=concat if last else None, cs_out=4 * self.chs, c_off=s * self.chs,
                                                  packs=packs, tracked=tracked, deferred=deferred if last else None, fold=fold)
+                keep()
                 x_relu = relu_only
             tape['streams'].append(recs)
         if deferred:
@@ -757,13 +878,15 @@ class Trunk:
             call('mmlf_bn_apply_relu4', arr(0), cs_of(self.chs), self.chs, arr(1), arr(2), ptr(concat), 4 * self.chs,
                  B, H, W, ptr(concat.absmax), _lib.stream_ptr())
             del deferred[:]
-        if save and relu_only:
+        if save and any(plan.slices):
             tape['concat'] = concat
         # (x_relu False: x is the concat buffer, whose ReLU mmlf_relu_bwd_slice applies per stream in backward)
         x, cs_x, x_relu, xmask = concat, 4 * self.chs, False, None
-        for spec in self.out_blocks:
-            x, cs_x, xmask = self._block_fwd(geo, spec, VAR_IDENTITY, x, cs_x, x_relu, xmask, p, train,
-                                             tape['out'] if save else None, packs=packs, tracked=tracked, fold=fold)
+        for k, spec in enumerate(self.out_blocks):
+            slot, keep = rec_of(save and plan.out[k] is not None, tape['out'])
+            x, cs_x, xmask = self._block_fwd(geo, spec, VAR_IDENTITY, x, cs_x, x_relu, xmask, p, train, slot, packs=packs,
+                                             tracked=tracked, fold=fold)
+            keep()
             x_relu = relu_only
         if tracked:
             # the shared stream nets' counters appear twice: two forwards per pass, as in the reference
@@ -778,10 +901,10 @@ class Trunk:
         return out, (tape if save else None)
 
     # ------------------------------------------------------------------ backward
-    def _block_bwd(self, geo, rec, p, grads, gy, cs_gy, c_off, need_dx, after_bn=None, overlap=False, packs=None):
+    def _block_bwd(self, geo, rec, bp, p, grads, gy, cs_gy, c_off, after_bn=None, overlap=False, packs=None):
         """gy: gradient w.r.t. the block output (grid, extent (H,W)).  Returns (dX grid tensor or None, event, keep).
-        grads None: no parameter gradient is wanted -- no weight-gradient launch, no side stream, and BatchNorm's pass 1 only
-        where its coefficients need the batch sums (train-mode statistics).
+        bp: the block's BlockPlan -- the launches that run, and nothing else decides one; grads holds the tensors of bp.want.
+        The unwanted partner of a wanted tensor goes nowhere (gw / gb = NULL) or to scratch (dgamma / dbeta).
         after_bn: called once this block's BatchNorm-backward kernels are enqueued.  overlap: run the
         first convolution's weight gradient on the side stream AFTER the data gradient is enqueued, so that
         it (matrix-core bound) runs beside the BatchNorm-backward kernels of the block underneath (HBM
@@ -798,9 +921,11 @@ class Trunk:
         packs = packs or {}
         f16 = CONV_MODE == 'f16x3' and self.ksize == 2
         bn = rec.bn                      # (False where a frozen evaluation folded BatchNorm into conv2: ReLU-only backward)
-        assert grads is None or rec.pk2d is None, 'a frozen forward (BatchNorm folded) has no parameter gradients'
-        if grads is not None:
-            gw1, gb1, gw2, gb2 = (grads[f'{pre}.{k}'] for k in ('0.weight', '0.bias', '2.weight', '2.bias'))
+        assert not bp.want or rec.pk2d is None, 'a frozen forward (BatchNorm folded) has no parameter gradients'
+        assert bool(bn) or not (bp.reduce or bp.apply), (pre, bp)
+        need_dx = bp.dgrad1
+        gw1, gb1, gw2, gb2, g3w, g3b = (grads[f'{pre}.{k}'] if k in bp.want else None
+                                        for k in ('0.weight', '0.bias', '2.weight', '2.bias', '3.weight', '3.bias'))
 
         # the ReLU of y in conv2's data gradient: by the bits conv1's forward launch left, or else by y itself
         y_relu = {'mask_in': rec.ymask} if rec.ymask is not None and f16 else {'ref': y, 'cs_ref': cs_mid}
@@ -814,42 +939,48 @@ class Trunk:
             x_relu = {'mask_in': rec.xmask} if rec.xmask is not None and f16 else {'ref': x, 'cs_ref': cs_x}
 
         # this block's gradient buffers, one zeroing launch: dz (behind BatchNorm), dy, dx
-        got = geo.bufs(([cs_mid] if bn else []) + [cs_mid] + ([cs_x] if need_dx else []), dev)
-        dy = got[1 if bn else 0]
+        css = ([cs_mid] if bp.apply else []) + ([cs_mid] if bp.dgrad2 else []) + ([cs_x] if need_dx else [])
+        got = geo.bufs(css, dev) if css else []
+        dy = got[1 if bp.apply else 0] if bp.dgrad2 else None
         dx = got[-1] if need_dx else None
+        dz = None
         if bn:
-            if grads is None and rec.eval:
-                # running statistics and nobody reads dgamma / dbeta: dz = k1 * g with k1 = gamma * invstd, the saved scale
-                coef = torch.zeros(3 * C, dtype=torch.float32, device=dev)
-                coef[:C].copy_(rec.scale)
-            else:
+            if bp.reduce:
                 coef = torch.empty(3 * C, dtype=torch.float32, device=dev)
-                if grads is None:       # the batch sums feed the coefficients; their dgamma / dbeta form goes to scratch
-                    dgb = ws.scratch('bn_dgamma_dbeta', 2 * C)
-                    dgamma, dbeta, acc = dgb[:C], dgb[C:2 * C], 0
-                else:
-                    dgamma, dbeta, acc = grads[f'{pre}.3.weight'], grads[f'{pre}.3.bias'], 1
+                # an unwanted dgamma / dbeta goes to scratch: the batch sums still feed the coefficients (or the other of the two)
+                dgb = ws.scratch('bn_dgamma_dbeta', 2 * C) if g3w is None or g3b is None else None
+                dgamma, dbeta = (dgb[:C] if g3w is None else g3w), (dgb[C:2 * C] if g3b is None else g3b)
+                acc = int(g3w is not None or g3b is not None)
                 call('mmlf_bn_bwd_reduce', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
                      ptr(p[f'{pre}.3.weight']), ptr(rec.smean), ptr(rec.sinv), ptr(dgamma), ptr(dbeta), acc, ptr(coef),
                      ptr(ws.partial), BN_BLOCKS, B, H, W, sp())
-                if rec.eval:
+                if rec.eval and bp.apply:
                     coef[C:].zero_()        # no batch-statistics terms: dz = k1 * g (dgamma / dbeta sums are the same)
-            dz = got[0]
-            call('mmlf_bn_bwd_apply', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
-                 ptr(rec.smean), ptr(coef), ptr(dz), cs_mid, B, H, W, ptr(dz.absmax), sp())
+            elif bp.apply:
+                # running statistics and nobody reads dgamma / dbeta: dz = k1 * g with k1 = gamma * invstd, formed as
+                # mmlf_bn_bwd_reduce forms it (the float64 product of gamma and the saved float32 invstd, rounded once), so that
+                # a frozen block hands down the bits the full backward does
+                assert rec.eval, (pre, bp)
+                coef = torch.zeros(3 * C, dtype=torch.float32, device=dev)
+                coef[:C].copy_((p[f'{pre}.3.weight'].double() * rec.sinv.double()).float())
+            if bp.apply:
+                dz = got[0]
+                call('mmlf_bn_bwd_apply', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
+                     ptr(rec.smean), ptr(coef), ptr(dz), cs_mid, B, H, W, ptr(dz.absmax), sp())
         else:
             assert c_off == 0 and cs_gy == cs_mid
             dz = gy
         if after_bn:
             after_bn()
         # conv2: weight / bias gradient, then data gradient fused with the ReLU of y
-        if grads is not None:
+        if bp.wgrad2:
             self._wgrad(geo, True, y, cs_mid, C, dz, cs_mid, C, gw2, gb2, var)
-        pk2d = rec.pk2d if rec.pk2d is not None else self._packed(packs, p, f'{pre}.2.weight', var, True)
-        self._dgrad(geo, True, dz, cs_mid, C, pk2d, C, dy, cs_mid, **y_relu)
+        if bp.dgrad2:
+            pk2d = rec.pk2d if rec.pk2d is not None else self._packed(packs, p, f'{pre}.2.weight', var, True)
+            self._dgrad(geo, True, dz, cs_mid, C, pk2d, C, dy, cs_mid, **y_relu)
         del dz, got
         # conv1: the same, with the ReLU (if any) of the block underneath
-        if overlap and need_dx and grads is not None:
+        if overlap and need_dx and bp.wgrad1:
             self._dgrad(geo, False, dy, cs_mid, C, self._packed(packs, p, f'{pre}.0.weight', var, True), spec.cin, dx, cs_x,
                         **x_relu)
             main = torch.cuda.current_stream()
@@ -861,7 +992,7 @@ class Trunk:
             # x and dy are read by the side stream: the caller keeps them alive until the main stream has waited
             # for `done` (no record_stream: deferred reuse makes the caching allocator grow and stall)
             return dx, done, (x, dy)
-        if grads is not None:
+        if bp.wgrad1:
             self._wgrad(geo, False, x, cs_x, spec.cin, dy, cs_mid, C, gw1, gb1, var)
         if need_dx:
             self._dgrad(geo, False, dy, cs_mid, C, self._packed(packs, p, f'{pre}.0.weight', var, True), spec.cin, dx, cs_x,
@@ -871,15 +1002,20 @@ class Trunk:
     def backward(self, p, tape, grad_output, grads, on_done=None, input_grads=None):
         """grad_output: (B,oc,H,W) NCHW.  grads: dict name -> tensor, ACCUMULATED into
         (the caller zeroes them), or None: no parameter gradient is formed (no weight-gradient launch at all; required
-        for a tape of forward(frozen=True)).  on_done(key) is called when every gradient of 'out_net.k' /
-        'in_net_id' / 'in_net_hv' has been enqueued (gradient-bucket all-reduce hook).
+        for a tape of forward(frozen=True)).  The dict holds the names the forward pass was given as trainable= (all of
+        _grad_names by default; a name of that set that is missing is an error, other names are not looked at).  The launches
+        are those of Trunk.plan for these names and input_grads.  on_done(key) is called exactly once per key, in the order
+        'out_net.k' ..., 'in_net_id', 'in_net_hv', when every gradient of the key has been enqueued -- for a key whose blocks
+        launch nothing, as soon as nothing more can come for it (gradient-bucket all-reduce hook).
         input_grads: four bools (streams H, V, I, D), the view stacks whose gradient is wanted; default none.  Returns a list
         of four entries: the (B, views, 3, H, W) float32 gradient of a wanted stack, None for the others.  The parameter
         gradients do not depend on it: the same weight-gradient launches in the same order."""
         geo, dev = tape['geo'], tape['device']
         check(grad_output, 'grad_output', dev, shape=(geo.B, self.oc, geo.H, geo.W), contiguous=False)
+        fplan = tape.get('plan')
         if grads is not None:
-            self._check_dict('grads', grads, self._grad_names, dev)
+            wanted = self._grad_names if fplan is None else [n for n in self._grad_names if n in fplan.trainable]
+            self._check_dict('grads', grads, wanted, dev)
         _Workspace.get(dev).enter_stream()
         B, H, W = geo.B, geo.H, geo.W
         cs = cs_of(self.oc)
@@ -889,6 +1025,15 @@ class Trunk:
         cs_g = cs
         want = [bool(w) for w in input_grads] if input_grads is not None else [False] * 4
         assert len(want) == 4
+        # this pass's plan: the forward's wanted names (none with grads=None) and the stacks asked for HERE; it may ask for
+        # less than the forward recorded for, never for more
+        bplan = self.plan(fplan.trainable if grads is not None else (), want, fplan.train, fplan.fold)
+
+        def rec_for(rec, bp):
+            if rec is None:
+                raise ValueError(f'Trunk.backward: the forward pass kept no record of {bp.prefix} (its trainable= / '
+                                 'input_grads= did not ask for what this backward needs)')
+            return rec
         dstacks = [None] * 4
         recs = tape['out']
         main = torch.cuda.current_stream()
@@ -904,10 +1049,19 @@ class Trunk:
 
         while recs:
             rec = recs.pop()
+            bp = bplan.out[len(recs)]
+            if bp is None:
+                # the block and everything beneath it launch nothing: its key is complete as soon as the block above is
+                g = None
+                settle()
+                if on_done:
+                    on_done(self.out_blocks[len(recs)].prefix)
+                continue
+            rec = rec_for(rec, bp)
             # (layers wider than one launch run their weight gradient as column blocks, the second of them on kernels the
             # register budget of the overlap was not drawn up for: they stay on the main stream)
             wide = OVERLAP_WGRAD and 128 <= rec.spec.cin <= MAX_OVERLAP_WIDTH and self.ksize == 2
-            g, event, keep = self._block_bwd(geo, rec, p, grads, g, cs_g, 0, True, after_bn=settle, overlap=wide,
+            g, event, keep = self._block_bwd(geo, rec, bp, p, grads, g, cs_g, 0, after_bn=settle, overlap=wide,
                                              packs=tape['packs'])
             settle()                        # (blocks without BatchNorm never called it)
             if event is not None:
@@ -920,16 +1074,24 @@ class Trunk:
             recs = tape['streams'][s]
             if s == 2:
                 settle()                    # out_net.0's weight gradient ran beside the first stream's BatchNorm kernels
+            if not bplan.stream_live[s]:
+                del recs[:]                 # a stream without a live block is skipped, its ReLU slice included
             gs, cs_s, off = g, cs_g, s * self.chs
-            if 'concat' in tape:
+            if bplan.slices[s]:
+                if 'concat' not in tape:
+                    raise ValueError('Trunk.backward: the forward pass kept no concat buffer for this backward')
                 # the stream's last ReLU wrote its slice of the concat buffer: the gradient behind it, as a compact tensor
                 cs_s, off = cs_of(self.chs), 0
                 gs = geo.buf(cs_s, dev)
                 relu_bwd_slice(geo, g, cs_g, s * self.chs, tape['concat'], cs_g, s * self.chs, self.chs, gs, cs_s)
             while recs:
                 rec = recs.pop()
-                gs, _, _ = self._block_bwd(geo, rec, p, grads, gs, cs_s, off, need_dx=bool(recs) or want[s],
-                                           packs=tape['packs'])
+                bp = bplan.streams[s][len(recs)]
+                if bp is None:              # (live blocks sit on top of a chain: nothing beneath this one runs either)
+                    del recs[:]
+                    break
+                rec = rec_for(rec, bp)
+                gs, _, _ = self._block_bwd(geo, rec, bp, p, grads, gs, cs_s, off, packs=tape['packs'])
                 cs_s, off = rec.cs_x, 0
             if want[s]:
                 # gs: the gradient of the stream's packed input, extent (H, W) at (1, 1), 3 views channels of cs_s

@@ -97,18 +97,20 @@ class _UNetTail(nn.Module):
 class _TrunkFn(torch.autograd.Function):
     """One autograd node for in_net_hv x2, in_net_id x2, concat and out_net: differentiable in the parameters and in the
     four view stacks.  Backward forms what autograd asks for (ctx.needs_input_grad): the gradient of each stack that requires
-    one, as a (B, views, 3, H, W) tensor, and the parameter gradients only if some parameter requires one -- a frozen
-    network used as a differentiable function of its inputs pays for no weight gradient."""
+    one, as a (B, views, 3, H, W) tensor, and the gradients of the parameters that require one -- both passes follow the plan
+    of exactly those (Trunk.plan): a partly frozen net pays for the rest only, and a frozen network used as a
+    differentiable function of its inputs pays for no weight gradient."""
 
     @staticmethod
     def forward(ctx, module, train, save, h, v, i, d, *params):
         p = module._tensor_dict()                       # buffers; parameters as passed (a replica's per-device copies)
         p.update(zip(module._param_names, (t.detach() for t in params)))
-        frozen = not any(ctx.needs_input_grad[7:])
+        # the step's plan (Trunk.plan): backward runs only where a parameter that requires a gradient, or a wanted stack, needs it
+        trainable = [n for n, need in zip(module._param_names, ctx.needs_input_grad[7:]) if need]
         with torch.no_grad():
             out, tape = module._trunk.forward(p, [h, v, i, d], train, save, input_grads=ctx.needs_input_grad[3:7],
-                                              frozen=frozen)
-        ctx.module, ctx.tape, ctx.p = module, tape, (p if save else None)
+                                              trainable=trainable)
+        ctx.module, ctx.tape, ctx.p, ctx.trainable = module, tape, (p if save else None), trainable
         return out
 
     @staticmethod
@@ -117,9 +119,9 @@ class _TrunkFn(torch.autograd.Function):
         if tape is None:
             raise RuntimeError('FeedForward: backward through a forward that saved nothing')
         ctx.tape = ctx.p = None
-        names = module._param_names
+        names = ctx.trainable                           # the flat gradient holds the wanted parameters only
         grads = None
-        if any(ctx.needs_input_grad[7:]):
+        if names:
             sizes = [p[n].numel() for n in names]
             flat = torch.zeros(sum(sizes), dtype=torch.float32, device=gout.device)
             grads, o = {}, 0
@@ -128,7 +130,7 @@ class _TrunkFn(torch.autograd.Function):
                 o += sz
         with torch.no_grad(), torch.cuda.device(gout.device):
             dstacks = module._trunk.backward(p, tape, gout, grads, input_grads=ctx.needs_input_grad[3:7])
-        return (None, None, None) + tuple(dstacks) + tuple(grads[n] if grads else None for n in names)
+        return (None, None, None) + tuple(dstacks) + tuple(grads.get(n) if grads else None for n in module._param_names)
 
 
 class _HeadUprFn(torch.autograd.Function):

@@ -206,6 +206,11 @@ class TrainStep:
         self.buckets = GradBuckets(self.layout, process_group, self._agreed_bucket_count()) if self.distributed else None
         self._grads = {name: self.grad[o:o + n].view_as(dict(model.named_parameters())[name])
                        for name, o, n in self.layout}
+        # the parameters that train, fixed here: a frozen one (requires_grad False) gets no gradient, so its slices of the flat
+        # gradient and of Adam's moments stay zero and the one Adam launch moves it by exactly 0 (the reference's
+        # optim.Adam skips a parameter without a gradient); the flat layout, the buckets and the launch keep their shape
+        self.trainable = frozenset(name for name, p in model.named_parameters() if p.requires_grad)
+        self._trainable_grads = {name: g for name, g in self._grads.items() if name in self.trainable}
         self._margin_mask = {}
         if self.distributed:   # every replica starts from rank 0's weights and buffers (DataParallel replicate)
             dist.broadcast(self.flat, 0, group=process_group)
@@ -276,6 +281,10 @@ class TrainStep:
     def __call__(self, h, v, i_, d, gt, mask, iteration):
         """One optimisation step on this rank's shard.  Returns the (rank-local) loss tensor."""
         model = self.model
+        for name, p in model.named_parameters():      # one flag read per parameter
+            if p.requires_grad != (name in self.trainable):
+                raise ValueError(f'TrainStep: requires_grad of {name!r} changed since construction (now {p.requires_grad}); '
+                                 'Adam\'s moments belong to the set fixed then -- build a new TrainStep')
         if self.eval_mode and iteration >= self.eval_mode_start:
             model.eval()
         else:
@@ -300,7 +309,7 @@ class TrainStep:
         model = self.model
         p = model._tensor_dict()
         with torch.no_grad():
-            out, tape = model._trunk.forward(p, [h, v, i_, d], model.training, True)
+            out, tape = model._trunk.forward(p, [h, v, i_, d], model.training, True, trainable=self.trainable)
             den = self._den_end(den)
             if self.multimodal:
                 loss, gout = self._multimodal_loss(out, gt, mask, den)
@@ -319,7 +328,7 @@ class TrainStep:
                 else:
                     loss, gout = loss_mod.native_loss(kind, out, gt, mask, grid, half, True, den)
             on_done = (lambda key: self.buckets.ready(self.grad, key)) if self.distributed else None
-            model._trunk.backward(p, tape, gout, self._grads, on_done)
+            model._trunk.backward(p, tape, gout, self._trainable_grads or None, on_done)
         return loss
 
     def _padded_mpi(self, mpi):
@@ -391,7 +400,8 @@ class TrainStep:
             loss = loss * (cnt / den.squeeze()).float() if cnt > 0 else loss
         loss.backward()
         for name, p in model.named_parameters():
-            self._grads[name].copy_(p.grad)
+            if p.grad is not None:          # (a frozen parameter: its slice of the flat gradient stays zero)
+                self._grads[name].copy_(p.grad)
             p.grad = None
         return loss.detach()
 
