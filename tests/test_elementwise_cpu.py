@@ -200,8 +200,11 @@ def test_gpu_shape_lists_reach_every_class(lister):
         pieces = {min(xt, W + 2 - x0) for _, W in te.SHIFT_PACK_FRAMES for x0 in range(0, W + 2, xt)}
         _covers_once(walk, cs // 4, sorted(pieces))
     assert set(te.SHIFT_PACK_VIEWS) >= {9, 7} and set(te.SHIFT_PACK_FRAMES) >= {(24, 24), (9, 40), (33, 17), (3, 2)}
-    sp = tuple(sorted({W + 2 for _, W in te.SHIFT_PACK_FRAMES}))            # every pitch here is one piece: below xt = 128
-    assert walk(8, ())[0] == (8, 32, 0) and pack_xt(32) == 128 and pack_xt(24) == 128 and max(sp) < 128
+    assert set(te.SHIFT_PACK_VIEWS) >= {1, 2} and set(te.SHIFT_PACK_FRAMES) >= {(1, 300), (300, 1)}
+    # the pieces of every pitch here at xt = 128: a pitch below 128 is one piece, the pitch of 302 is two whole pieces and 46
+    sp = tuple(sorted({min(128, W + 2 - x0) for _, W in te.SHIFT_PACK_FRAMES for x0 in range(0, W + 2, 128)}))
+    assert walk(8, ())[0] == (8, 32, 0) and pack_xt(32) == 128 and pack_xt(24) == 128 and pack_xt(8) == 128
+    assert max(sp) == 128 and 302 % 128 in sp and 3 in sp
     w7, rows7 = walk(6, sp)
     assert w7 == (6, 42, 4) and 4 in rows7                                  # a carry | a pitch below dx: one pair per thread
     assert {seen for seen, _, _ in rows7[4]['threads']} == {0, 1}

@@ -88,9 +88,11 @@ def test_shift_hip_matches_reference():
 # (csrc/row_walk.h).  9 views: cs = 32, 8 groups, 256 % 8 = 0 -- never a carry.  7 views: cs = 24, 6 groups, the walk moves on
 # by (42, 4): at a pitch of 4 (frame (3, 2)) a thread is out of the row on its first step; at a pitch of 45 (frame (2, 43))
 # threads carry in mid-row (x = 0 -> 43) and leave through the carry (x = 2 -> 44 -> 45).  tests/test_elementwise_cpu.py holds
-# these lists to that.
-SHIFT_PACK_VIEWS = (9, 7)
-SHIFT_PACK_FRAMES = [(24, 24), (9, 40), (33, 17), (3, 2), (2, 43)]
+# these lists to that.  One row (every vertical roll is the identity clamp) at a pitch of 302: three pieces of the 128-position
+# tile; one column; one view (half = 0: nothing is sheared) and two (an even count: views at -1 and 0).  mmlf_shift_views, the
+# other side of the comparison, is held to the oracle's bits at the same kinds of frame by tests/test_gpu_data_kernels.py.
+SHIFT_PACK_VIEWS = (9, 7, 1, 2)
+SHIFT_PACK_FRAMES = [(24, 24), (9, 40), (33, 17), (3, 2), (2, 43), (1, 300), (300, 1)]
 
 
 @pytest.mark.gpu

@@ -465,3 +465,157 @@ LOSS_STRIDE_FRAME = (1, 1024, 2049)
 LOSS_NBLOCKS = [1, 3, 63, 64, 65, 1024, 4096]
 LOSS_NBLOCKS_FRAMES = [(3, 5, 7), (2, 1, 300)]
 ADAM_N = [1, 255, 256, 257, 2097153]
+
+
+# ------------------------------------------------------------------ data side and validation side: numpy references
+# (tests/test_data_refs_cpu.py pins them to the goldens; tests/test_gpu_data_kernels.py holds the kernels to them.)  The shear,
+# the patch chain and Contrast are float32 restatements, operation for operation: the kernels must give these BITS.  The
+# ensemble posterior and the discretised mixture are float64 with a per-element bound that counts the float32 roundings on the
+# kernel's path, under the assumption that the device expf is good to 1 ulp (U32 = 2^-24 is half an ulp).
+U32 = 2.0 ** -24
+PATCH_NAMES = ('h', 'v', 'i', 'd', 'center', 'gt', 'mpi', 'mask')
+
+
+def _oracle():
+    from oracle import oracle as orc
+    return orc
+
+
+def shift_table_ref(disps, views):
+    """hci4d.py:934-938 per (member, view): integer shifts (s0, s1) int32 and weights (1 - alpha, alpha) float32, from
+    math.modf / copysign on doubles: what mmlf_shift_views takes as tab_s / tab_w"""
+    import math
+    half = int(views / 2)
+    tab_s, tab_w = np.zeros((len(disps), views, 2), np.int32), np.zeros((len(disps), views, 2), np.float32)
+    for s, disp in enumerate(disps):
+        for k in range(views):
+            alpha, s0 = math.modf(float(disp) * (k - half))
+            s1 = s0 + math.copysign(1.0, s0)
+            tab_s[s, k] = (int(s0), int(s1))
+            tab_w[s, k] = (1.0 - abs(alpha), abs(alpha))
+    return tab_s, tab_w
+
+
+def shift_ref(stacks, disps):
+    """four stacks (views, 3, H, W) -> four arrays (S, views, 3, H, W) float32: oracle.shift_views per disparity"""
+    orc = _oracle()
+    per = [orc.shift_views(stacks, float(d)) for d in disps]
+    return [np.stack([p[i] for p in per]).astype(np.float32) for i in range(4)]
+
+
+def patch_ref(scene, params):
+    """One sample of the training patch chain with every parameter given: params = dict(ps, f, disp, y0, x0, rot, flags, mat,
+    bright); flags: 1 shift | 2 colour | 4 brightness.  The kernel's documented order (include/mmlf_hip.h): tf_downsample(f),
+    tf_shift(disp) under flag 1, ONE crop of ps x ps at (y0, x0) of the down-sampled frame, rot x tf_rotate90 (the mask is not
+    rotated), tf_redist_color under flag 2, tf_brightness under flag 4; gt and mpi[:, 4] take / f always and - disp under flag 1.
+    Returns (h, v, i, d, center, gt, mpi) float32 and the mask as int64."""
+    orc = _oracle()
+    p = params
+    data = tuple(np.array(a, copy=True) for a in scene[:8])
+    data = orc.tf_downsample(data, int(p['f']))
+    if p['flags'] & 1:
+        data = orc.tf_shift(data, p['disp'])
+    data = orc.tf_crop(data, (p['ps'], p['ps']), (p['y0'], p['x0']))
+    for _ in range(p['rot']):
+        data = orc.tf_rotate90(data)
+    if p['flags'] & 2:
+        data = orc.tf_redist_color(data, np.asarray(p['mat'], np.float64))
+    if p['flags'] & 4:
+        data = orc.tf_brightness(data, p['bright'])
+    for a in data[:7]:
+        assert a.dtype == np.float32, 'precondition: the chain stays in float32'
+    return (*[np.ascontiguousarray(a) for a in data[:7]], np.ascontiguousarray(data[7]).astype(np.int64))
+
+
+def contrast_ref(stacks4, center, alpha, mean32):
+    """Contrast (hci4d.py:740-751) for a GIVEN float32 mean: x * float32(alpha) + mean32 * float32(1 - alpha), each operation
+    rounded to float32.  stacks4: the four stacks of one sample; returns ([four stacks], center)."""
+    a, b, m = np.float32(alpha), np.float32(1.0 - alpha), np.float32(mean32)
+    off = np.float32(m * b)
+    f = lambda x: (np.asarray(x, np.float32) * a).astype(np.float32) + off   # noqa: E731
+    return [f(x) for x in stacks4], f(center)
+
+
+def ensamble_reduce_ref(means, logvars, grid):
+    """means, logvars (S, B, H, W) float32, grid (K,) float32 -> (idx, mean, logvar, ref, bound): idx (B, H, W) the FIRST
+    minimum of logvars over the members (np.argmin: the reference's rule on the CPU and that of the kernel's strict <), mean
+    and logvar gathered there (exact), ref (B, K, H, W) float64 = (1/S) sum_j exp(t_j) / (2 b_j) with b_j = exp(logvar_j),
+    t_j = -|grid_k - mean_j| / b_j, and the bound of the float32 kernel's error: per term (6 + 4 |t_j|) U32 -- the subtraction
+    U32, b 2 U32, the division U32 make t off by 4 U32, so exp(t) by 4 |t| U32 plus 2 U32 of its own, 1 / (2 b) adds 3 U32 and
+    the product U32 -- plus (S + 1) U32 of the sum for S sequential additions of positive terms and the division, plus 1e-37
+    for underflow."""
+    S = means.shape[0]
+    idx = np.argmin(logvars, 0)
+    mean = np.take_along_axis(means, idx[None], 0)[0]
+    logvar = np.take_along_axis(logvars, idx[None], 0)[0]
+    gk = np.asarray(grid, np.float32).astype(np.float64).reshape(1, -1, 1, 1)
+    ref = np.zeros((means.shape[1], gk.size, *means.shape[2:]), np.float64)
+    werr = np.zeros_like(ref)
+    for j in range(S):
+        b = np.exp(logvars[j].astype(np.float64))[:, None]
+        t = -np.abs(gk - means[j].astype(np.float64)[:, None]) / b
+        term = np.exp(t) / (2.0 * b)
+        ref += term
+        werr += (6.0 + 4.0 * np.abs(t)) * term
+    ref /= S
+    bound = U32 / S * werr + (S + 1) * U32 * ref + 1e-37
+    return idx, mean, logvar, ref, bound
+
+
+def ensamble_posterior_f32(means, logvars, grid):
+    """the kernel's float32 arithmetic in numpy, operation for operation (laplace_pdf and the sequential sum): what the bound of
+    ensamble_reduce_ref is tried against without a GPU"""
+    S = means.shape[0]
+    gk = np.asarray(grid, np.float32).reshape(1, -1, 1, 1)
+    acc = np.zeros((means.shape[1], gk.size, *means.shape[2:]), np.float32)
+    for j in range(S):
+        b = np.exp(logvars[j].astype(np.float32))[:, None]
+        a = np.float32(1.0) / (np.float32(2.0) * b)
+        t = -np.abs(gk - means[j][:, None]) / b
+        acc = acc + a * np.exp(t)
+    return acc / np.float32(S)
+
+
+def lmm_edges(n_bins, x_min, x_max):
+    """validate/cli.py:90-103: the n_bins + 1 float64 bin edges"""
+    step = (x_max - x_min) / n_bins
+    return np.linspace(x_min - step / 2.0, x_max + step / 2.0, n_bins + 1)
+
+
+def _cdf_laplace64(x, m, v):
+    z = (x - m) / v
+    with np.errstate(over='ignore'):
+        return np.where(x < m, np.exp(z) / 2.0, 1.0 - np.exp(-z) / 2.0)
+
+
+def lmm_ref(means, logvars, edges, exp32=None):
+    """means, logvars (S, B, H, W) float32, edges (n_bins + 1,) float64 -> (ref, bound), both (B, n_bins, H, W) float64:
+    ref = (1/S) sum_s cdf(edge_k+1) - cdf(edge_k) of Laplace(mean_s, v_s) with v = float64(np.exp(float32 logvars)), as
+    metrics.laplace_to_discrete states it.  The kernel is float64 except for v = (double)expf(logvar): a 1 ulp expf against
+    numpy's float32 exp moves v by at most 2^-22 relative, and each exp(-|z|) / 2 term by w(z) 2^-22, w(z) = |z| exp(-|z|) / 2:
+    bound = 2^-22 / S * sum_s (w(z0_s) + w(z1_s)) + 4e-16 (the cancellation in 1 - exp(-z) / 2 and the float64 sum).
+    exp32: another float32 exponential (the CPU tests try the bound with it)."""
+    S = means.shape[0]
+    e = np.asarray(edges, np.float64)
+    e0, e1 = e[:-1].reshape(1, -1, 1, 1), e[1:].reshape(1, -1, 1, 1)
+    ref = np.zeros((means.shape[1], e.size - 1, *means.shape[2:]), np.float64)
+    werr = np.zeros_like(ref)
+    w = lambda z: np.abs(z) * np.exp(-np.abs(z)) / 2.0   # noqa: E731
+    for s in range(S):
+        lv = logvars[s].astype(np.float32)
+        v = (np.exp(lv) if exp32 is None else exp32(lv)).astype(np.float32).astype(np.float64)[:, None]
+        m = means[s].astype(np.float64)[:, None]
+        ref += _cdf_laplace64(e1, m, v) - _cdf_laplace64(e0, m, v)
+        werr += w((e0 - m) / v) + w((e1 - m) / v)
+    return ref / S, 2.0 ** -22 / S * werr + 4e-16
+
+
+def lmm_mass_ref(means, logvars, edges):
+    """(B, H, W) float64: cdf(last edge) - cdf(first edge) of the mixture: what an image's bin masses add up to"""
+    e = np.asarray(edges, np.float64)
+    tot = np.zeros(means.shape[1:], np.float64)
+    for s in range(means.shape[0]):
+        v = np.exp(logvars[s].astype(np.float32)).astype(np.float64)
+        m = means[s].astype(np.float64)
+        tot += _cdf_laplace64(e[-1], m, v) - _cdf_laplace64(e[0], m, v)
+    return tot / means.shape[0]
