@@ -5,9 +5,11 @@ step is a call through the C ABI (include/mmlf_hip.h).
 
 Layout and indexing are described in include/mmlf_hip.h and DESIGN.md section 3.
 """
+import contextlib
 import ctypes
 import os
 import threading
+from collections import namedtuple
 
 import torch
 
@@ -111,7 +113,9 @@ class _Workspace:
 
     @classmethod
     def get(cls, device):
-        table = cls._tls.__dict__.setdefault('table', {})
+        table = getattr(cls._tls, 'table', None)
+        if table is None:
+            table = cls._tls.table = {}
         key = (device.type, device.index)
         ws = table.get(key)
         if ws is None:
@@ -120,10 +124,11 @@ class _Workspace:
 
     def __init__(self, device):
         self.device = device
-        self.wgrad = None
-        self.wgrad_side = None                       # workspace of weight-gradient launches on the side stream
         self.side = torch.cuda.Stream(device=device) if device.type == 'cuda' else None
         self.partial = torch.empty(2 * 512 * max(BN_BLOCKS, LOSS_BLOCKS) + 8, dtype=torch.float64, device=device)
+        self._packs = {}                 # packed_filters: signature -> (signature, table, store, views, columns)
+        self._last_stream = None         # enter_stream
+        self._scratch = {}               # scratch: (name, side) -> float32 buffer
 
     def packed_filters(self, items):
         """f16-split packed forms of many filters from ONE launch (mmlf_pack_filters_h2).  items: list of
@@ -144,7 +149,7 @@ class _Workspace:
         lib = _lib.load()
         sig = tuple((w.data_ptr(), w.shape[0], w.shape[1], int(var), int(dg)) for _, w, var, dg in items)
         self.enter_stream()
-        caches = self.__dict__.setdefault('_packs', {})
+        caches = self._packs
         cache = caches.get(sig)
         if cache is None:
             if len(caches) >= 4:                       # (weights re-allocated: drop the stale entries)
@@ -182,19 +187,19 @@ class _Workspace:
         if self.device.type != 'cuda':
             return
         cur = torch.cuda.current_stream(self.device)
-        last = self.__dict__.get('_last_stream')
+        last = self._last_stream
         if last is not None and last != cur:
             cur.wait_event(last.record_event())
         self._last_stream = cur
 
-    def scratch(self, name, n):
-        """a float32 scratch buffer of at least n elements, reused across calls of this thread on this stream"""
-        if not name.endswith('_side'):      # (side-stream launches are ordered by their own events, _block_bwd)
+    def scratch(self, name, n, side=False):
+        """a float32 scratch buffer of at least n elements, reused across calls of this thread on this stream.  side: the one
+        of that name for side-stream launches, which share no scratch with the main stream's and are ordered by their events"""
+        if not side:
             self.enter_stream()
-        t = getattr(self, name, None)
+        t = self._scratch.get((name, side))
         if t is None or t.numel() < n:
-            t = torch.empty(n, dtype=torch.float32, device=self.device)
-            setattr(self, name, t)
+            t = self._scratch[name, side] = torch.empty(n, dtype=torch.float32, device=self.device)
         return t
 
     def wgrad_ws(self, geo, cin, cout, side=False):
@@ -202,12 +207,7 @@ class _Workspace:
         n = int(query(cin, cout, geo.B, geo.H, geo.W))
         if n < 0:
             raise RuntimeError(f'wgrad: unsupported channels {cin}->{cout}')
-        name = 'wgrad_side' if side else 'wgrad'
-        if not side:                 # (the side stream's launches are ordered by their own events, _block_bwd)
-            self.enter_stream()
-        if getattr(self, name) is None or getattr(self, name).numel() < n:
-            setattr(self, name, torch.empty(n, dtype=torch.float32, device=self.device))
-        return getattr(self, name)
+        return self.scratch('wgrad', n, side)
 
 
 # 'f16x3': 2-way f16 split of power-of-two-scaled operands, 3 MFMA passes (f32-equivalent accuracy, 5.3x the
@@ -252,6 +252,17 @@ def _tic():
 def _toc(events, tag, flops, nbytes):
     events[1].record()
     PROFILE.append((tag, flops, events[0], events[1], nbytes))
+
+
+@contextlib.contextmanager
+def _timed(tag, flops, nbytes):
+    """PROFILE: the launches inside the `with` block between two events, as one entry"""
+    events = _tic()
+    yield
+    _toc(events, tag, flops, nbytes)
+
+
+_UNTIMED = contextlib.nullcontext()      # what a launch that PROFILE does not time runs under
 
 
 def _amax_of(geo, t, cs):
@@ -330,31 +341,30 @@ def wgrad(geo, x, cs_in, cin, g, cs_g, cout, g_shift, gw, gb, variant, workspace
     form; x is not read); gb None: the weight gradient alone."""
     if cout <= THIN_MAX_N and cin >= THIN_MIN_K and cs_in <= 512:
         # a matrix-vector product (the BASE / UPR head): plain float32 FMAs, bound by reading x once
-        ws = _Workspace.get(x.device).scratch('thin_wgrad_side' if side else 'thin_wgrad', int(_lib.load().mmlf_conv2x2_wgrad_thin_workspace_floats(cin)))
+        ws = _Workspace.get(x.device).scratch('thin_wgrad', int(_lib.load().mmlf_conv2x2_wgrad_thin_workspace_floats(cin)), side)
         call('mmlf_conv2x2_wgrad_thin', ptr(x), cs_in, cin, ptr(g), cs_g, cout, g_shift, ptr(gw), ptr(gb), variant, 1,
              ptr(ws), geo.B, geo.H, geo.W, _lib.stream_ptr())
         return
     args = (ptr(x), cs_in, cin, ptr(g), cs_g, cout, g_shift, ptr(gw), ptr(gb), variant, 1, ptr(workspace),
             geo.B, geo.H, geo.W)
-    prof = PROFILE is not None and cin >= 256 and cout >= 256 and gw is not None
-    if prof:
-        events = _tic()
-    if CONV_MODE == 'f16x3':
-        ax, ag = _amax_of(geo, x, cs_in), _amax_of(geo, g, cs_g)
-        if CHECK_EXTENTS:
-            _audit('mmlf_audit_wgrad_h2', (cs_in, cin, cs_g, cout, g_shift, geo.B, geo.H, geo.W), 7,
-                   f'wgrad {cin}->{cout} B={geo.B} {geo.H}x{geo.W} g_shift={g_shift}',
-                   {'in': (0, x, 0), 'g': (1, g, 0), 'gw': (2, gw, 0), 'gb': (3, gb, 0), 'workspace': (4, workspace, 0),
-                    'in_amax': (5, ax, 0), 'g_amax': (6, ag, 0)})
-        call('mmlf_conv2x2_wgrad_h2', *args, ptr(ax), ptr(ag), _lib.stream_ptr())
-    else:
-        call('mmlf_conv2x2_wgrad_split' if CONV_MODE == 'bf16x6' else 'mmlf_conv2x2_wgrad', *args, _lib.stream_ptr())
-    if prof:
+    timed = _UNTIMED
+    if PROFILE is not None and cin >= 256 and cout >= 256 and gw is not None:
         # algorithmic FLOPs: the convolution's valid output positions x Cout x 4 taps x Cin, 2 FLOP per MAC (the
         # gradient of a pad-1 convolution lives at grid offset 0 with extent (H+1, W+1), of a pad-0 one at (1, 1))
         vh, vw = (geo.H + 1, geo.W + 1) if g_shift == 0 else (geo.H, geo.W)
         nbytes = 4.0 * geo.B * (cin * (geo.H * geo.W if g_shift == 0 else (geo.H + 1) * (geo.W + 1)) + cout * vh * vw)
-        _toc(events, 'wgrad_side' if side else 'wgrad', 2.0 * geo.B * vh * vw * cout * 4 * cin, nbytes)
+        timed = _timed('wgrad_side' if side else 'wgrad', 2.0 * geo.B * vh * vw * cout * 4 * cin, nbytes)
+    with timed:
+        if CONV_MODE == 'f16x3':
+            ax, ag = _amax_of(geo, x, cs_in), _amax_of(geo, g, cs_g)
+            if CHECK_EXTENTS:
+                _audit('mmlf_audit_wgrad_h2', (cs_in, cin, cs_g, cout, g_shift, geo.B, geo.H, geo.W), 7,
+                       f'wgrad {cin}->{cout} B={geo.B} {geo.H}x{geo.W} g_shift={g_shift}',
+                       {'in': (0, x, 0), 'g': (1, g, 0), 'gw': (2, gw, 0), 'gb': (3, gb, 0), 'workspace': (4, workspace, 0),
+                        'in_amax': (5, ax, 0), 'g_amax': (6, ag, 0)})
+            call('mmlf_conv2x2_wgrad_h2', *args, ptr(ax), ptr(ag), _lib.stream_ptr())
+        else:
+            call('mmlf_conv2x2_wgrad_split' if CONV_MODE == 'bf16x6' else 'mmlf_conv2x2_wgrad', *args, _lib.stream_ptr())
 
 
 def conv(geo, x, cs_in, K, packed, bias, N, out, cs_out, out_shift, vh, vw, relu, ref=None, cs_ref=0,
@@ -373,28 +383,27 @@ def conv(geo, x, cs_in, K, packed, bias, N, out, cs_out, out_shift, vh, vw, relu
         return
     n_store = cs_out if n_store is None else n_store
     # bench.py's per-launch timing: the 280-wide launches (tag 'conv') and the 70 -> 70 stream-layer launches ('conv70')
-    prof = PROFILE is not None and ((K >= 256 and N >= 256) or (K == N and 64 <= K < 128))
-    if prof:
-        events = _tic()
-    args = (ptr(x), cs_in, K, ptr(packed), ptr(bias), N, ptr(out) + 4 * out_off, cs_out, n_store, out_shift, vh, vw,
-            geo.B, geo.H, geo.W, int(relu), ptr(ref), cs_ref)
-    if CONV_MODE == 'f16x3':
-        ax = _amax_of(geo, x, cs_in)
-        if CHECK_EXTENTS:
-            _audit('mmlf_audit_conv_h2', (cs_in, K, N, cs_out, n_store, out_shift, cs_ref, geo.B, geo.H, geo.W), 9,
-                   f'conv {K}->{N} B={geo.B} {geo.H}x{geo.W} shift={out_shift}',
-                   {'in': (0, x, 0), 'packed': (1, packed, 0), 'bias': (2, bias, 0), 'out': (3, out, out_off),
-                    'ref': (4, ref, 0), 'in_amax': (5, ax, 0), 'out_amax': (6, aout, 0), 'bn_partial': (7, bn_partial, 0),
-                    'mask_out': (8, mask_out, 0), 'mask_in': (8, mask_in, 0)})
-        call('mmlf_conv2x2_h2', *args, ptr(ax), ptr(aout), ptr(bn_partial), ptr(mask_out), ptr(mask_in), _lib.stream_ptr())
-    else:
-        call('mmlf_conv2x2_split' if CONV_MODE == 'bf16x6' else 'mmlf_conv2x2', *args, _lib.stream_ptr())
-    if prof:
+    timed = _UNTIMED
+    if PROFILE is not None and ((K >= 256 and N >= 256) or (K == N and 64 <= K < 128)):
         # algorithmic FLOPs of this launch: valid output positions x N x 4 taps x K, 2 FLOP per MAC; algorithmic BYTES: the
         # input's and the output's stored extents once each (a pad-1 convolution reads (H, W) and writes (H+1, W+1), a pad-0
         # one the other way round), float32, unpadded channels
         nbytes = 4.0 * geo.B * (K * (geo.H * geo.W if out_shift == 0 else (geo.H + 1) * (geo.W + 1)) + N * vh * vw)
-        _toc(events, 'conv' if K >= 256 else 'conv70', 2.0 * geo.B * vh * vw * N * 4 * K, nbytes)
+        timed = _timed('conv' if K >= 256 else 'conv70', 2.0 * geo.B * vh * vw * N * 4 * K, nbytes)
+    args = (ptr(x), cs_in, K, ptr(packed), ptr(bias), N, ptr(out) + 4 * out_off, cs_out, n_store, out_shift, vh, vw,
+            geo.B, geo.H, geo.W, int(relu), ptr(ref), cs_ref)
+    with timed:
+        if CONV_MODE == 'f16x3':
+            ax = _amax_of(geo, x, cs_in)
+            if CHECK_EXTENTS:
+                _audit('mmlf_audit_conv_h2', (cs_in, K, N, cs_out, n_store, out_shift, cs_ref, geo.B, geo.H, geo.W), 9,
+                       f'conv {K}->{N} B={geo.B} {geo.H}x{geo.W} shift={out_shift}',
+                       {'in': (0, x, 0), 'packed': (1, packed, 0), 'bias': (2, bias, 0), 'out': (3, out, out_off),
+                        'ref': (4, ref, 0), 'in_amax': (5, ax, 0), 'out_amax': (6, aout, 0), 'bn_partial': (7, bn_partial, 0),
+                        'mask_out': (8, mask_out, 0), 'mask_in': (8, mask_in, 0)})
+            call('mmlf_conv2x2_h2', *args, ptr(ax), ptr(aout), ptr(bn_partial), ptr(mask_out), ptr(mask_in), _lib.stream_ptr())
+        else:
+            call('mmlf_conv2x2_split' if CONV_MODE == 'bf16x6' else 'mmlf_conv2x2', *args, _lib.stream_ptr())
 
 
 # ---------------------------------------------------------------------------------------------- 3x3 filters (--model_ksize 3)
@@ -413,13 +422,9 @@ def conv3(geo, x, cs_in, K, packed, bias, N, out, cs_out, relu, ref=None, cs_ref
                f'conv3x3 {K}->{N} B={geo.B} {geo.H}x{geo.W}',
                {'in': (0, x, 0), 'packed': (1, packed, 0), 'bias': (2, bias, 0), 'out': (3, out, out_off), 'ref': (4, ref, 0)})
     prof = PROFILE is not None and K >= 256 and N >= 256
-    if prof:
-        events = _tic()
-    call('mmlf_conv3x3', ptr(x), cs_in, K, ptr(packed), ptr(bias), N, ptr(out) + 4 * out_off, cs_out, n_store,
-         geo.B, geo.H, geo.W, int(relu), ptr(ref), cs_ref, _lib.stream_ptr())
-    if prof:
-        nbytes = 4.0 * geo.B * geo.H * geo.W * (K + N)
-        _toc(events, 'conv3x3', 2.0 * geo.B * geo.H * geo.W * N * 9 * K, nbytes)
+    with _timed('conv3x3', 2.0 * geo.B * geo.H * geo.W * N * 9 * K, 4.0 * geo.B * geo.H * geo.W * (K + N)) if prof else _UNTIMED:
+        call('mmlf_conv3x3', ptr(x), cs_in, K, ptr(packed), ptr(bias), N, ptr(out) + 4 * out_off, cs_out, n_store,
+             geo.B, geo.H, geo.W, int(relu), ptr(ref), cs_ref, _lib.stream_ptr())
 
 
 def wgrad3(geo, x, cs_in, cin, g, cs_g, cout, gw, gb, variant, workspace):
@@ -440,22 +445,85 @@ class BlockSpec:
         self.prefix, self.cin, self.cout, self.bn = prefix, cin, cout, bn
 
 
-class _Rec:
-    """What a block's forward leaves on the tape for its backward.  x / cs_x: the block's input; x_relu: x is the output of a
-    block without BatchNorm (whose trailing ReLU the data gradient of conv1 applies), xmask: the bits of that ReLU if it left
-    any; y: conv1's output behind its ReLU, ymask: that ReLU as bits (f16 split); z: conv2's output where BatchNorm or
-    nothing follows; scale ... sinv: BatchNorm's coefficients and saved statistics; eval: they are the RUNNING statistics.
-    bn: backward goes through BatchNorm (spec.bn, unless the forward folded it into conv2: a frozen evaluation, whose block is
-    then a ReLU-only one with the filter whose data-gradient form is pk2d)."""
-    __slots__ = ('spec', 'var', 'x', 'cs_x', 'x_relu', 'xmask', 'y', 'ymask', 'z', 'scale', 'shift', 'smean', 'sinv', 'eval',
-                 'bn', 'pk2d')
+# One block of the trunk, as Trunk.sites lists them in forward order.  chain: 0 ... 3 a stream (H, V, I, D), 4 out_net; k: the
+# block's position in its chain; var: the stream's filter variant; last: the chain's last block.
+Site = namedtuple('Site', 'index chain k spec var last')
 
-    def __init__(self, spec, var, x, cs_x, x_relu, xmask, y, ymask, z):
-        self.spec, self.var, self.x, self.cs_x, self.x_relu, self.xmask = spec, var, x, cs_x, x_relu, xmask
-        self.y, self.ymask, self.z = y, ymask, z
+# A grid activation: tensor, channel stride; relu: a ReLU wrote it, which the data gradient of the convolution that reads it
+# applies (conv1's output; the output of a block without BatchNorm), mask: the bits of that ReLU if its launch left any.
+_Act = namedtuple('_Act', 't cs relu mask')
+# Channels [off, off + C) of a grid tensor of channel stride cs: a gradient on its way down, or where a block's output goes.
+_Slice = namedtuple('_Slice', 't cs off')
+# A convolution of a block: second: its pad-0 one (False: its pad-1 one), K -> N channels, the stream's variant, the packed
+# filter, the bias and, for the thin kernels, the OIHW master filter.  A weight gradient is described by the first four.
+_Filter = namedtuple('_Filter', 'second K N var packed bias master', defaults=(None, None, None))
+
+
+class _Rec:
+    """What a block's forward leaves on the tape for its backward.  x: the block's input (x.relu: the output of a block
+    without BatchNorm, whose trailing ReLU the data gradient of conv1 applies); y: conv1's output behind its ReLU; z: conv2's
+    output where BatchNorm or nothing follows; scale ... sinv: BatchNorm's coefficients and saved statistics; eval: they are
+    the RUNNING statistics.  bn: backward goes through BatchNorm (spec.bn, unless the forward folded it into conv2: a frozen
+    evaluation, whose block is then a ReLU-only one with the filter whose data-gradient form is pk2d)."""
+    __slots__ = ('spec', 'var', 'x', 'y', 'z', 'scale', 'shift', 'smean', 'sinv', 'eval', 'bn', 'pk2d')
+
+    def __init__(self, site, x, y, z):
+        self.spec, self.var, self.x, self.y, self.z = site.spec, site.var, x, y, z
         self.scale = self.shift = self.smean = self.sinv = None
-        self.eval = False
-        self.bn, self.pk2d = spec.bn, None
+        self.eval, self.bn, self.pk2d = False, site.spec.bn, None
+
+
+class _Tape:
+    """One pass over the trunk: what its blocks share and what forward leaves for backward (Trunk.forward returns it).  plan:
+    the forward's Plan (None: nothing is saved); packs: the step's prepacked filters; tracked: the BatchNorm counters the pass
+    moves; deferred: (z, scale, shift) of the streams' last blocks, whose BatchNorm-apply runs as ONE pass (None: each block
+    applies its own); concat: kept behind forward for mmlf_relu_bwd_slice only; recs[site.index]: a live block's record."""
+    __slots__ = ('geo', 'device', 'p', 'train', 'fold', 'plan', 'packs', 'tracked', 'deferred', 'concat', 'recs')
+
+    def __init__(self, geo, device, p=None, train=False, fold=False, plan=None, packs=None, sites=0):
+        self.geo, self.device, self.p, self.train, self.fold, self.plan = geo, device, p, train, fold, plan
+        self.packs, self.tracked, self.deferred, self.concat, self.recs = packs or {}, [], None, None, [None] * sites
+
+
+class _SideWgrad:
+    """The weight gradient that one backward pass runs on the workspace's side stream (OVERLAP_WGRAD), and the pass's on_done
+    hook.  A wide block's first convolution's weight gradient is launched there AFTER the block's data gradient is enqueued,
+    which is all the BatchNorm-backward kernels of the block underneath need.  At most one launch is pending; settle() makes
+    the main stream wait for it.  A workspace without a side stream (no CUDA device) overlaps nothing and touches no stream."""
+    __slots__ = ('main', 'side', 'pending', 'kept', 'on_done')
+
+    def __init__(self, ws, on_done, enabled):
+        self.side = ws.side if enabled else None
+        self.main = torch.cuda.current_stream() if self.side is not None else None
+        self.pending, self.kept, self.on_done = None, None, on_done      # pending: (the launch's end, its on_done key)
+
+    def takes(self, cin):
+        # (wider layers run as column blocks, on kernels outside the overlap's register budget: main stream, DESIGN.md 4.14)
+        return self.side is not None and 128 <= cin <= MAX_OVERLAP_WIDTH
+
+    def launch(self, key, keep, run):
+        """run() on the side stream, behind everything the main stream has enqueued; settle() reports key.  keep: the
+        tensors it reads, held (no record_stream: deferred reuse makes the caching allocator grow and stall) until the next
+        out_net block has enqueued its launches (_block_bwd) -- one block longer than settle() needs, and where the
+        allocator's peak has always been."""
+        ready = self.main.record_event()
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(ready)
+            run()
+            self.pending, self.kept = (self.side.record_event(), key), keep
+
+    def settle(self):
+        """the main stream waits for the pending launch, whose key is complete then"""
+        if self.pending is not None:
+            self.main.wait_event(self.pending[0])
+            if self.on_done:
+                self.on_done(self.pending[1])
+            self.pending = None
+
+    def done(self, key):
+        """every gradient of `key` is enqueued -- unless its weight gradient is the pending launch: settle() says so then"""
+        if self.on_done and (self.pending is None or self.pending[1] != key):
+            self.on_done(key)
 
 
 class BlockPlan:
@@ -500,6 +568,10 @@ class Plan:
         self.streams, self.out = streams, out
         self.stream_live = [any(b is not None for b in blocks) for blocks in streams]
         self.slices = [relu_only and live for live in self.stream_live]
+
+    def of(self, site):
+        """the BlockPlan of a Site, None where the block launches nothing"""
+        return self.out[site.k] if site.chain == 4 else self.streams[site.chain][site.k]
 
     def blocks(self):
         """the live blocks in backward order"""
@@ -553,10 +625,15 @@ class Trunk:
         if c > MAX_WIDTH[ksize] or oc > MAX_OC:
             raise ValueError(f'native trunk: 4*model_chs = {c} (max {MAX_WIDTH[ksize]} with {ksize}x{ksize} filters), '
                              f'{oc} output channels (max {MAX_OC})')
+        # every block once, in forward order (streams H, V, I, D, then out_net); reversed: backward's order.  The ONE listing
+        # that _numel, plan, _prepack, forward and backward walk
+        chains = [(var, blocks) for _, var, blocks in self.streams] + [(VAR_IDENTITY, self.out_blocks)]
+        sites = [(c, k, spec, var, k == len(blocks) - 1) for c, (var, blocks) in enumerate(chains) for k, spec in enumerate(blocks)]
+        self.sites = tuple(Site(i, *site) for i, site in enumerate(sites))
         # state_dict key -> element count of every parameter and BatchNorm buffer the blocks read through raw pointers
         # (check_params); h / v and i / d share their nets' keys
         self._numel = {}
-        for spec in [b for _, _, blocks in self.streams for b in blocks] + self.out_blocks:
+        for spec in (site.spec for site in self.sites):
             n = {'0.weight': spec.cout * spec.cin * ksize * ksize, '0.bias': spec.cout,
                  '2.weight': spec.cout * spec.cout * ksize * ksize, '2.bias': spec.cout}
             if spec.bn is True:
@@ -564,8 +641,7 @@ class Trunk:
                 n['3.num_batches_tracked'] = 1
             self._numel.update({f'{spec.prefix}.{k}': v for k, v in n.items()})
         self._grad_names = [n for n in self._numel if n.endswith(('.weight', '.bias'))]     # what backward accumulates into
-        self._checked = {}
-        self._plans = {}
+        self._checked, self._plans = {}, {}
 
     def _check_dict(self, what, d, names, dev):
         """every d[name]: present, on `dev`, contiguous, float32 (the BatchNorm counter int64), of the element count its block
@@ -610,21 +686,18 @@ class Trunk:
             return cached
         if len(self._plans) >= 64:
             self._plans.clear()
-
-        def chain(blocks, below, x_wanted):
-            """below: something beneath the chain is live (its first block's dx is needed); x_wanted: the chain's input
-            gradient itself is"""
-            out, live = [], below or x_wanted
-            for k, spec in enumerate(blocks):
-                want = {n[len(spec.prefix) + 1:] for n in wanted if n.startswith(spec.prefix + '.')}
-                need_dx = live                       # the block beneath is live, or the stack's gradient is wanted
-                live = live or bool(want)
-                out.append(BlockPlan(spec.prefix, want, spec.bn is True and not fold, train, need_dx) if live else None)
-            return out
-
-        streams = [chain(blocks, False, want_x[s]) for s, (_, _, blocks) in enumerate(self.streams)]
-        out = chain(self.out_blocks, any(b is not None for blocks in streams for b in blocks), False)
-        made = self._plans[key] = Plan(wanted, want_x, bool(train), bool(fold), streams, out, not self.batchnorm or bool(fold))
+        chains = [[] for _ in range(5)]
+        for site in self.sites:
+            spec = site.spec
+            if site.k == 0:
+                # a chain's first block needs dx where its stack's gradient is wanted (a stream) or a stream is live (out_net)
+                live = want_x[site.chain] if site.chain < 4 else any(b is not None for blocks in chains for b in blocks)
+            want = {n[len(spec.prefix) + 1:] for n in wanted if n.startswith(spec.prefix + '.')}
+            need_dx = live                           # the block beneath is live, or the stack's gradient is wanted
+            live = live or bool(want)
+            chains[site.chain].append(BlockPlan(spec.prefix, want, spec.bn is True and not fold, train, need_dx) if live else None)
+        made = self._plans[key] = Plan(wanted, want_x, bool(train), bool(fold), chains[:4], chains[4],
+                                       not self.batchnorm or bool(fold))
         return made
 
     # ------------------------------------------------------------------ filters
@@ -636,167 +709,169 @@ class Trunk:
         if CONV_MODE != 'f16x3' or dev.type != 'cuda' or self.ksize != 2:
             return {}
         items = []
-
-        def add(name, var, dgrad):
-            items.append(((name, var, dgrad), p[name], var, dgrad))
-
-        def block(spec, var, bp):
+        add = lambda name, var, dgrad: items.append(((name, var, dgrad), p[name], var, dgrad))       # noqa: E731
+        for site in self.sites:
+            spec, var, bp = site.spec, site.var, plan.of(site) if plan else None
             thin = spec.cout <= THIN_MAX_N and spec.cin >= THIN_MIN_K      # the head's first conv runs from the master filter
             own2 = not (fold and spec.bn is True)
             if not thin:
                 add(f'{spec.prefix}.0.weight', var, False)
             if own2:
                 add(f'{spec.prefix}.2.weight', var, False)
-            if bp is not None:
-                if own2 and bp.dgrad2:
-                    add(f'{spec.prefix}.2.weight', var, True)
-                if bp.dgrad1:
-                    add(f'{spec.prefix}.0.weight', var, True)
-
-        for s, (_, var, blocks) in enumerate(self.streams):
-            for k, spec in enumerate(blocks):
-                block(spec, var, plan.streams[s][k] if plan else None)
-        for k, spec in enumerate(self.out_blocks):
-            block(spec, VAR_IDENTITY, plan.out[k] if plan else None)
+            if bp is not None and own2 and bp.dgrad2:
+                add(f'{spec.prefix}.2.weight', var, True)
+            if bp is not None and bp.dgrad1:
+                add(f'{spec.prefix}.0.weight', var, True)
         return _Workspace.get(dev).packed_filters(items)
 
     def _pack(self, w, var, dgrad):
         return (pack_filter3 if self.ksize == 3 else pack_filter)(w, var, dgrad)
 
-    def _packed(self, packs, p, name, var, dgrad):
+    def _packed(self, tape, name, var, dgrad):
         """the packed form of filter `name`: from the step's prepack, or else packed now"""
-        pk = packs.get((name, var, dgrad))
-        return pk if pk is not None else self._pack(p[name], var, dgrad)
+        pk = tape.packs.get((name, var, dgrad))
+        return pk if pk is not None else self._pack(tape.p[name], var, dgrad)
+
+    def _f16(self):
+        return CONV_MODE == 'f16x3' and self.ksize == 2      # ReLU bits, BatchNorm sums from conv2: the f16-split 2x2 kernels'
 
     # ------------------------------------------------------------------ the two convolutions of a block, by kernel size
     # 2x2: conv1 (pad 1) takes extent (H, W) at grid offset (1, 1) to (H+1, W+1) at offset 0, conv2 (pad 0) takes it back; a
-    # data gradient goes the way of the other convolution's forward.  3x3: "same" convolutions, one geometry for all.
-    def _conv(self, geo, second, x, cs_in, K, packed, bias, N, out, cs_out, relu, ref=None, cs_ref=0, n_store=None, out_off=0,
-              **only2x2):
-        """forward of a block's first / second convolution.  only2x2: bn_partial, mask_out, mask_in, w_master, variant of
-        `conv`, for what the 3x3 kernels do not have (the callers' capability conditions leave them None there)"""
+    # data gradient goes the way of the other convolution's forward: _extent[second] is the launch's (out_shift, vh, vw).
+    # 3x3: "same" convolutions, one geometry for all.
+    _extent = (lambda geo: (0, geo.H + 1, geo.W + 1), lambda geo: (geo.P + 1, geo.H, geo.W))
+
+    def _conv(self, geo, x, f, out, off=None, stats=None):
+        """forward of the convolution f (_Filter) from the activation x into `out` (_Act: its ReLU rides in the epilogue and
+        leaves out.mask).  off: `out` is shared with other blocks and channels [off, off + f.N) of it are stored; None: the
+        block's own buffer, stored at its whole channel stride.  stats: the float64 buffer for BatchNorm's per-workgroup sums.
+        The 3x3 kernels have no mask, sums or thin form (the callers' capability conditions leave them None there)."""
+        n_store, out_off = (out.cs, 0) if off is None else (f.N, off)
         if self.ksize == 3:
-            assert all(v is None for v in only2x2.values()), only2x2
-            conv3(geo, x, cs_in, K, packed, bias, N, out, cs_out, relu, ref=ref, cs_ref=cs_ref, n_store=n_store, out_off=out_off)
+            assert out.mask is None and stats is None and f.master is None, (f, out.mask, stats)
+            conv3(geo, x.t, x.cs, f.K, f.packed, f.bias, f.N, out.t, out.cs, out.relu, n_store=n_store, out_off=out_off)
             return
-        out_shift, vh, vw = (geo.P + 1, geo.H, geo.W) if second else (0, geo.H + 1, geo.W + 1)
-        conv(geo, x, cs_in, K, packed, bias, N, out, cs_out, out_shift, vh, vw, relu, ref=ref, cs_ref=cs_ref, n_store=n_store,
-             out_off=out_off, **only2x2)
+        conv(geo, x.t, x.cs, f.K, f.packed, f.bias, f.N, out.t, out.cs, *self._extent[f.second](geo), out.relu,
+             n_store=n_store, out_off=out_off, bn_partial=stats, mask_out=out.mask, w_master=f.master, variant=f.var)
 
-    def _dgrad(self, geo, second, g, cs_g, K, packed, N, dx, cs_dx, **relu_of):
-        """data gradient of a block's first / second convolution (packed: its dgrad form); relu_of: `ref`, `cs_ref` or
-        `mask_in` of a ReLU in front of that convolution, applied in the epilogue"""
-        self._conv(geo, not second, g, cs_g, K, packed, None, N, dx, cs_dx, False, **relu_of)
-
-    def _wgrad(self, geo, second, x, cs_in, cin, g, cs_g, cout, gw, gb, var, side=False):
-        """weight + bias gradient of a block's first / second convolution, accumulated into gw / gb"""
-        ws = _Workspace.get(x.device).wgrad_ws(geo, cin, cout, side=side)
+    def _dgrad(self, geo, g, f, dx, x):
+        """data gradient of the convolution f (f.packed: its dgrad form) from the gradient g of its output into dx (_Slice,
+        both at offset 0).  x: the activation the convolution read; the ReLU behind it, if any, is applied in the epilogue: by
+        x itself or, in the f16 split, by the bits the launch that wrote x left -- that launch and this one have the same
+        (B, H, W), N, out_shift and a buffer of channel stride x.cs of their own, so they run the same kernel and epilogue
+        orientation and agree on the private word layout."""
+        relu = {}
+        if x.relu:
+            relu = {'mask_in': x.mask} if x.mask is not None and self._f16() else {'ref': x.t, 'cs_ref': x.cs}
         if self.ksize == 3:
-            wgrad3(geo, x, cs_in, cin, g, cs_g, cout, gw, gb, var, ws)
+            conv3(geo, g.t, g.cs, f.N, f.packed, None, f.K, dx.t, dx.cs, False, **relu)
+            return
+        conv(geo, g.t, g.cs, f.N, f.packed, None, f.K, dx.t, dx.cs, *self._extent[not f.second](geo), False, **relu)
+
+    def _wgrad(self, geo, f, x, g, into, side=False):
+        """weight + bias gradient of the convolution f from its input x and the gradient g of its output, accumulated into
+        the pair `into` = (gw, gb)"""
+        ws = _Workspace.get(x.t.device).wgrad_ws(geo, f.K, f.N, side=side)
+        if self.ksize == 3:
+            wgrad3(geo, x.t, x.cs, f.K, g.t, g.cs, f.N, *into, f.var, ws)
         else:
-            wgrad(geo, x, cs_in, cin, g, cs_g, cout, geo.P + 1 if second else 0, gw, gb, var, ws, side=side)
+            wgrad(geo, x.t, x.cs, f.K, g.t, g.cs, f.N, geo.P + 1 if f.second else 0, *into, f.var, ws, side=side)
 
     # ------------------------------------------------------------------ forward
-    def _block_fwd(self, geo, spec, var, x, cs_x, x_relu, xmask, p, train, rec_list, out=None, cs_out=None, c_off=0, packs=None,
-                   tracked=None, deferred=None, fold=False):
-        """One block: conv1 (pad 1) -> ReLU -> conv2 (pad 0), then BatchNorm -> ReLU (bn True), ReLU (bn False) or nothing (the
-        head).  conv1's ReLU always rides in its epilogue; conv2's does where conv2 is the block's last operation.
-        x: grid tensor (extent H,W at (1,1)); x_relu: x is the output of a block without BatchNorm, xmask: the bits of that
-        ReLU if it left any (both kept for backward).  rec_list: where to leave what backward needs, None = nothing is saved.
-        out (a stream's last block): the block output goes to the channel slice [c_off, c_off + cout) of the concat buffer.
-        deferred (a list): the BatchNorm-apply + ReLU pass into `out` is NOT launched; (z, scale, shift) is appended
-        and the caller applies all four streams' last blocks in one pass over the concat buffer (Trunk.forward).
-        fold: eval-mode BatchNorm is folded into conv2 (inference, and the saving forward of a frozen net: Trunk.forward).
-        Returns (output grid tensor, its channel stride, the bits of its ReLU mask or None)."""
-        dev = x.device
-        ws = _Workspace.get(dev)
-        B, H, W = geo.B, geo.H, geo.W
-        C, cs_mid = spec.cout, cs_of(spec.cout)
-        pre = spec.prefix
-        w1, b1, w2, b2 = p[f'{pre}.0.weight'], p[f'{pre}.0.bias'], p[f'{pre}.2.weight'], p[f'{pre}.2.bias']
-        packs = packs or {}
-        save = rec_list is not None
-        f16 = CONV_MODE == 'f16x3' and self.ksize == 2             # ReLU bits and fused statistics: the f16-split kernels'
-        thin = C <= THIN_MAX_N and spec.cin >= THIN_MIN_K and self.ksize == 2     # the head: matrix-vector kernels, y is tiny
-        bits = save and f16 and not thin
-        folded = spec.bn is True and fold                          # BatchNorm folded into conv2
-        relu2 = spec.bn is False or folded                         # conv2 is the block's last operation: it writes the output
-        fused_stats = spec.bn is True and train and f16            # BatchNorm's statistics from conv2's epilogue
-        new_out = spec.bn is not None and out is None              # the block output is a buffer of its own
-        pk1 = None if thin else self._packed(packs, p, f'{pre}.0.weight', var, False)
-        if spec.bn is False:      # (these blocks pack conv2's filter ahead of conv1's launch)
-            pk2 = self._packed(packs, p, f'{pre}.2.weight', var, False)
-        got = geo.bufs([cs_mid] * ((1 if relu2 else 2) + (1 if new_out else 0)), dev)   # one zeroing launch for all
-        y = got[0]
-        z = None if relu2 else got[1]
-        if new_out:
-            out, cs_out, c_off = got[-1], cs_mid, 0
-        ymask = geo.relu_mask(dev) if bits else None
-        # the mask of the block's output is read by the data gradient of the NEXT block's first convolution (_block_bwd):
-        # a slice of the concat buffer has no such consumer (mmlf_relu_bwd_slice reads the activations)
-        omask = geo.relu_mask(dev) if bits and relu2 and new_out else None
-        head = {'w_master': w1, 'variant': var} if thin else {}    # (straight from the master filter)
-        self._conv(geo, False, x, cs_x, spec.cin, pk1, b1, C, y, cs_mid, True, mask_out=ymask, **head)
-        if folded:
-            # BatchNorm(eval) is a per-channel affine map -> fold it into conv2 and fuse the ReLU
-            coef = torch.empty(2 * C, dtype=torch.float32, device=dev)
-            call('mmlf_bn_coeffs_eval', ptr(p[f'{pre}.3.weight']), ptr(p[f'{pre}.3.bias']), ptr(p[f'{pre}.3.running_mean']),
-                 ptr(p[f'{pre}.3.running_var']), self.eps, ptr(coef), ptr(coef[C:]), C, _lib.stream_ptr())
-            w2f, b2f = torch.empty_like(w2), torch.empty_like(b2)
-            call('mmlf_fold_bn_eval3x3' if self.ksize == 3 else 'mmlf_fold_bn_eval', ptr(w2), ptr(b2), ptr(coef), ptr(coef[C:]),
-                 ptr(w2f), ptr(b2f), C, C, _lib.stream_ptr())
-            pk2, b2 = self._pack(w2f, var, False), b2f
-        elif spec.bn is not False:
-            pk2 = self._packed(packs, p, f'{pre}.2.weight', var, False)
-        rec = None
-        if save:
-            rec = _Rec(spec, var, x, cs_x, x_relu, xmask, y, ymask, z)
-            rec_list.append(rec)
-            if folded:
-                # backward is the ReLU-only block's, through the FOLDED filter (the weights are frozen: no gradient of theirs)
-                rec.bn, rec.pk2d = False, self._pack(w2f, var, True)
-        if relu2:
-            self._conv(geo, True, y, cs_mid, C, pk2, b2, C, out, cs_out, True, n_store=cs_out if new_out else C, out_off=c_off,
-                       mask_out=omask)
-            return out, cs_out, omask
-        self._conv(geo, True, y, cs_mid, C, pk2, b2, C, z, cs_mid, False, bn_partial=ws.partial if fused_stats else None)
-        if spec.bn is None:
-            return z, cs_mid, None
-        coef = torch.empty(4 * C, dtype=torch.float32, device=dev)
-        scale, shift, smean, sinv = coef[:C], coef[C:2 * C], coef[2 * C:3 * C], coef[3 * C:]
-        g, bt = p[f'{pre}.3.weight'], p[f'{pre}.3.bias']
-        rm, rv = p[f'{pre}.3.running_mean'], p[f'{pre}.3.running_var']
-        if train:
-            if fused_stats:
-                nblk = int(_lib.load().mmlf_conv2x2_blocks(C, C, B, H, W))
-                call('mmlf_bn_stats_finalize', ptr(ws.partial), nblk, C, ptr(g), ptr(bt), ptr(rm), ptr(rv),
-                     self.momentum, self.eps, ptr(smean), ptr(sinv), ptr(scale), ptr(shift), B, H, W,
-                     _lib.stream_ptr())
+    def _bn_fwd(self, tape, spec, z, rec):
+        """(scale, shift, smean, sinv) of a block's BatchNorm.  Train mode: the batch statistics of z (conv2's output) --
+        from the sums conv2's epilogue left (f16 split) or a pass over z -- which also move the running statistics; eval
+        mode: the running statistics' coefficients, and under a tape (rec: the block's record) the statistics themselves.
+        z None: the eval coefficients alone, for the fold into conv2 (smean, sinv: None)."""
+        geo, p, pre, C, sp = tape.geo, tape.p, spec.prefix, spec.cout, _lib.stream_ptr
+        coef = torch.empty((2 if z is None else 4) * C, dtype=torch.float32, device=tape.device)
+        scale, shift = coef[:C], coef[C:2 * C]
+        smean, sinv = (None, None) if z is None else (coef[2 * C:3 * C], coef[3 * C:])
+        g, bt, rm, rv = (p[f'{pre}.3.{k}'] for k in ('weight', 'bias', 'running_mean', 'running_var'))
+        if tape.train:
+            partial = _Workspace.get(tape.device).partial
+            if self._f16():
+                nblk = int(_lib.load().mmlf_conv2x2_blocks(C, C, geo.B, geo.H, geo.W))
+                call('mmlf_bn_stats_finalize', ptr(partial), nblk, C, ptr(g), ptr(bt), ptr(rm), ptr(rv),
+                     self.momentum, self.eps, ptr(smean), ptr(sinv), ptr(scale), ptr(shift), geo.B, geo.H, geo.W, sp())
             else:
-                call('mmlf_bn_stats_train', ptr(z), cs_mid, C, ptr(g), ptr(bt), ptr(rm), ptr(rv), self.momentum,
-                     self.eps, ptr(smean), ptr(sinv), ptr(scale), ptr(shift), ptr(ws.partial), BN_BLOCKS, B, H, W,
-                     _lib.stream_ptr())
-            if tracked is None:
-                p[f'{pre}.3.num_batches_tracked'].add_(1)
-            else:
-                tracked.append(p[f'{pre}.3.num_batches_tracked'])
+                call('mmlf_bn_stats_train', ptr(z), cs_of(C), C, ptr(g), ptr(bt), ptr(rm), ptr(rv), self.momentum,
+                     self.eps, ptr(smean), ptr(sinv), ptr(scale), ptr(shift), ptr(partial), BN_BLOCKS, geo.B, geo.H, geo.W, sp())
+            tape.tracked.append(p[f'{pre}.3.num_batches_tracked'])
         else:
-            call('mmlf_bn_coeffs_eval', ptr(g), ptr(bt), ptr(rm), ptr(rv), self.eps, ptr(scale), ptr(shift), C,
-                 _lib.stream_ptr())
-            if save:
+            call('mmlf_bn_coeffs_eval', ptr(g), ptr(bt), ptr(rm), ptr(rv), self.eps, ptr(scale), ptr(shift), C, sp())
+            if rec is not None:
                 # eval-mode BatchNorm under autograd (reference train/cli.py:227-230, --train_eval_mode): the
                 # statistics are constants, so backward is dz = g * gamma * invstd with the RUNNING statistics
                 smean.copy_(rm)
                 sinv.copy_(torch.rsqrt(rv.double() + self.eps).float())
                 rec.eval = True
-        if deferred is not None:
-            deferred.append((z, scale, shift))
-        else:
-            call('mmlf_bn_apply_relu', ptr(z), cs_mid, C, ptr(scale), ptr(shift), ptr(out), cs_out, c_off,
-                 cs_out if new_out else C, B, H, W, ptr(out.absmax), _lib.stream_ptr())
-        if save:
+        if rec is not None:
             rec.scale, rec.shift, rec.smean, rec.sinv = scale, shift, smean, sinv
-        return out, cs_out, None
+        return scale, shift, smean, sinv
+
+    def _block_fwd(self, tape, site, x, dest=None):
+        """One block: conv1 (pad 1) -> ReLU -> conv2 (pad 0), then BatchNorm -> ReLU (bn True), ReLU (bn False) or nothing (the
+        head).  conv1's ReLU always rides in its epilogue; conv2's does where conv2 is the block's last operation: a block
+        without BatchNorm, or one whose eval-mode BatchNorm is folded into conv2 (tape.fold: inference, and the saving forward
+        of a frozen net).  x: the input (_Act; extent H,W at (1,1)).  A live block of tape.plan leaves its record in tape.recs.
+        dest (a stream's last block): the slice of the concat buffer the output goes to; with tape.deferred the BatchNorm-apply
+        + ReLU pass into it is NOT launched but left to Trunk.forward's one pass for all four streams.  Returns the output."""
+        geo, p, dev, spec, var = tape.geo, tape.p, tape.device, site.spec, site.var
+        C, cs_mid, pre = spec.cout, cs_of(spec.cout), spec.prefix
+        w1, b1, w2, b2 = p[f'{pre}.0.weight'], p[f'{pre}.0.bias'], p[f'{pre}.2.weight'], p[f'{pre}.2.bias']
+        save = tape.plan is not None and tape.plan.of(site) is not None
+        f16 = self._f16()
+        thin = C <= THIN_MAX_N and spec.cin >= THIN_MIN_K and self.ksize == 2     # the head: matrix-vector kernels, y is tiny
+        bits = save and f16 and not thin
+        folded = spec.bn is True and tape.fold                     # BatchNorm folded into conv2
+        relu2 = spec.bn is False or folded                         # conv2 is the block's last operation: it writes the output
+        fused_stats = spec.bn is True and tape.train and f16       # BatchNorm's statistics from conv2's epilogue
+        new_out = spec.bn is not None and dest is None             # the block output is a buffer of its own
+        pk1 = None if thin else self._packed(tape, f'{pre}.0.weight', var, False)
+        if spec.bn is False:      # (these blocks pack conv2's filter ahead of conv1's launch)
+            pk2 = self._packed(tape, f'{pre}.2.weight', var, False)
+        got = geo.bufs([cs_mid] * ((1 if relu2 else 2) + (1 if new_out else 0)), dev)   # one zeroing launch for all
+        z = None if relu2 else got[1]
+        off = None if dest is None else dest.off                   # (None: a buffer of the block's own, stored at its whole stride)
+        if new_out:
+            dest = _Slice(got[-1], cs_mid, 0)
+        ymask = geo.relu_mask(dev) if bits else None
+        # the mask of the block's output is read by the data gradient of the NEXT block's first convolution (_block_bwd):
+        # a slice of the concat buffer has no such consumer (mmlf_relu_bwd_slice reads the activations)
+        omask = geo.relu_mask(dev) if bits and relu2 and new_out else None
+        y = _Act(got[0], cs_mid, True, ymask)
+        self._conv(geo, x, _Filter(False, spec.cin, C, var, pk1, b1, w1 if thin else None), y)   # (thin: from the master filter)
+        if folded:
+            # BatchNorm(eval) is a per-channel affine map -> fold it into conv2 and fuse the ReLU
+            scale, shift, _, _ = self._bn_fwd(tape, spec, None, None)
+            w2f, b2f = torch.empty_like(w2), torch.empty_like(b2)
+            call('mmlf_fold_bn_eval3x3' if self.ksize == 3 else 'mmlf_fold_bn_eval', ptr(w2), ptr(b2), ptr(scale), ptr(shift),
+                 ptr(w2f), ptr(b2f), C, C, _lib.stream_ptr())
+            pk2, b2 = self._pack(w2f, var, False), b2f
+        elif spec.bn is not False:
+            pk2 = self._packed(tape, f'{pre}.2.weight', var, False)
+        rec = None
+        if save:
+            rec = tape.recs[site.index] = _Rec(site, x, y, z)
+            if folded:
+                # backward is the ReLU-only block's, through the FOLDED filter (the weights are frozen: no gradient of theirs)
+                rec.bn, rec.pk2d = False, self._pack(w2f, var, True)
+        conv2 = _Filter(True, C, C, var, pk2, b2)
+        if relu2:
+            out = _Act(dest.t, dest.cs, True, omask)
+            self._conv(geo, y, conv2, out, off)
+            return out
+        self._conv(geo, y, conv2, _Act(z, cs_mid, False, None), stats=_Workspace.get(dev).partial if fused_stats else None)
+        if spec.bn is None:
+            return _Act(z, cs_mid, False, None)
+        scale, shift, _, _ = self._bn_fwd(tape, spec, z, rec)
+        if tape.deferred is not None and off is not None:
+            tape.deferred.append((z, scale, shift))
+        else:
+            call('mmlf_bn_apply_relu', ptr(z), cs_mid, C, ptr(scale), ptr(shift), ptr(dest.t), dest.cs, dest.off,
+                 dest.cs if new_out else C, geo.B, geo.H, geo.W, ptr(dest.t.absmax), _lib.stream_ptr())
+        return _Act(dest.t, dest.cs, False, None)
 
     def forward(self, p, stacks, train, save, packed=None, input_grads=None, frozen=False, trainable=None):
         """stacks: four (B, views, 3, H, W) contiguous float32 device tensors.  They, the grid tensors of `packed` and every
@@ -836,168 +911,128 @@ class Trunk:
         _Workspace.get(dev).enter_stream()
         # BatchNorm folded into conv2: inference, and the frozen evaluation that is differentiated in its inputs (3x3 trunks
         # have no ReLU-only backward and keep the unfolded form under a tape)
-        if frozen:
-            trainable = ()
-        plan = self.plan(trainable, input_grads, train) if save else None
+        plan = self.plan(() if frozen else trainable, input_grads, train) if save else None
         fold = self.batchnorm and not train and (not save or plan.fold)
-        relu_only = not self.batchnorm or fold                  # every block below the head ends in conv2's own ReLU
-        packs = self._prepack(p, dev, plan, fold)
-        tracked = []                  # BatchNorm counters of this pass: ONE increment launch at its end
-        tape = {'geo': geo, 'device': dev, 'streams': [], 'out': [], 'packs': packs, 'plan': plan}
-
-        def rec_of(live, recs):
-            """where a block leaves its record: a one-entry list for a live block, whose record (or None) joins `recs`"""
-            slot = [] if live else None
-            return slot, lambda: recs.append(slot[0] if slot else None)
+        tape = _Tape(geo, dev, p, train, fold, plan, self._prepack(p, dev, plan, fold), len(self.sites))
+        cs_in, cs_cat = cs_of(cin0), 4 * self.chs
         if packed is not None:
-            concat, xs = geo.buf(4 * self.chs, dev), list(xs_in)
+            tape.concat, xs = geo.buf(cs_cat, dev), list(xs_in)
         else:
-            concat, *xs = geo.bufs([4 * self.chs] + [cs_of(cin0)] * 3, dev)
-            xs.append(geo.buf(cs_of(cin0), dev))
+            tape.concat, *xs = geo.bufs([cs_cat] + [cs_in] * 3, dev)
+            xs.append(geo.buf(cs_in, dev))
         # the four streams' last BatchNorm-apply passes write quarter rows of the concat buffer: one pass for all four
-        # (whole rows) when they are real passes (not folded into conv2) and the channel count allows it
-        deferred = [] if (not fold and self.chs % 2 == 0 and all(b[-1].bn for _, _, b in self.streams)) else None
-        for s, (key, var, blocks) in enumerate(self.streams):
-            x = xs[s]
-            if packed is None:
-                call('mmlf_pack_nchw', ptr(stacks[s]), cin0, ptr(x), cs_of(cin0), B, H, W, ptr(x.absmax), _lib.stream_ptr())
-            cs_x = cs_of(cin0)
-            recs = []
-            x_relu, xmask = False, None
-            for k, spec in enumerate(blocks):
-                last = k == len(blocks) - 1
-                slot, keep = rec_of(save and plan.streams[s][k] is not None, recs)
-                x, cs_x, xmask = self._block_fwd(geo, spec, var, x, cs_x, x_relu, xmask, p, train, slot,
-                                                 out=concat if last else None, cs_out=4 * self.chs, c_off=s * self.chs,
-                                                 packs=packs, tracked=tracked, deferred=deferred if last else None, fold=fold)
-                keep()
-                x_relu = relu_only
-            tape['streams'].append(recs)
-        if deferred:
-            arr = lambda k: (ctypes.c_void_p * 4)(*[ptr(d[k]) for d in deferred])
-            call('mmlf_bn_apply_relu4', arr(0), cs_of(self.chs), self.chs, arr(1), arr(2), ptr(concat), 4 * self.chs,
-                 B, H, W, ptr(concat.absmax), _lib.stream_ptr())
-            del deferred[:]
-        if save and any(plan.slices):
-            tape['concat'] = concat
-        # (x_relu False: x is the concat buffer, whose ReLU mmlf_relu_bwd_slice applies per stream in backward)
-        x, cs_x, x_relu, xmask = concat, 4 * self.chs, False, None
-        for k, spec in enumerate(self.out_blocks):
-            slot, keep = rec_of(save and plan.out[k] is not None, tape['out'])
-            x, cs_x, xmask = self._block_fwd(geo, spec, VAR_IDENTITY, x, cs_x, x_relu, xmask, p, train, slot, packs=packs,
-                                             tracked=tracked, fold=fold)
-            keep()
-            x_relu = relu_only
-        if tracked:
+        # (whole rows) when they are real passes (not folded into conv2)
+        if self.batchnorm and not fold:
+            tape.deferred = []
+        for site in self.sites:
+            s = site.chain
+            if site.k == 0 and s < 4:
+                x = _Act(xs[s], cs_in, False, None)
+                if packed is None:
+                    call('mmlf_pack_nchw', ptr(stacks[s]), cin0, ptr(x.t), cs_in, B, H, W, ptr(x.t.absmax), _lib.stream_ptr())
+            elif site.k == 0:
+                if tape.deferred:
+                    arr = lambda k: (ctypes.c_void_p * 4)(*[ptr(d[k]) for d in tape.deferred])
+                    call('mmlf_bn_apply_relu4', arr(0), cs_of(self.chs), self.chs, arr(1), arr(2), ptr(tape.concat), cs_cat,
+                         B, H, W, ptr(tape.concat.absmax), _lib.stream_ptr())
+                tape.deferred = None
+                # (no trailing ReLU: mmlf_relu_bwd_slice applies the concat buffer's per stream in backward)
+                x = _Act(tape.concat, cs_cat, False, None)
+            x = self._block_fwd(tape, site, x, _Slice(tape.concat, cs_cat, s * self.chs) if site.last and s < 4 else None)
+        if tape.tracked:
             # the shared stream nets' counters appear twice: two forwards per pass, as in the reference
             # (feed_forward.py:222-235 calls in_net_hv for h and v) -- one entry per tensor with its count, since a
             # multi-tensor launch must not hold the same tensor twice
             counts = {}
-            for t in tracked:
+            for t in tape.tracked:
                 counts.setdefault(t.data_ptr(), [t, 0])[1] += 1
             torch._foreach_add_([t for t, _ in counts.values()], [n for _, n in counts.values()])
         out = torch.empty((B, self.oc, H, W), dtype=torch.float32, device=dev)
-        call('mmlf_unpack_nchw', ptr(x), cs_x, ptr(out), self.oc, B, H, W, _lib.stream_ptr())
+        call('mmlf_unpack_nchw', ptr(x.t), x.cs, ptr(out), self.oc, B, H, W, _lib.stream_ptr())
+        if not (save and any(plan.slices)):
+            tape.concat = None               # (kept for mmlf_relu_bwd_slice alone)
         return out, (tape if save else None)
 
     # ------------------------------------------------------------------ backward
-    def _block_bwd(self, geo, rec, bp, p, grads, gy, cs_gy, c_off, after_bn=None, overlap=False, packs=None):
-        """gy: gradient w.r.t. the block output (grid, extent (H,W)).  Returns (dX grid tensor or None, event, keep).
-        bp: the block's BlockPlan -- the launches that run, and nothing else decides one; grads holds the tensors of bp.want.
-        The unwanted partner of a wanted tensor goes nowhere (gw / gb = NULL) or to scratch (dgamma / dbeta).
-        after_bn: called once this block's BatchNorm-backward kernels are enqueued.  overlap: run the
-        first convolution's weight gradient on the side stream AFTER the data gradient is enqueued, so that
-        it (matrix-core bound) runs beside the BatchNorm-backward kernels of the block underneath (HBM
-        bound), which only need the data gradient; event: that launch's end, keep: the tensors to keep alive until
-        the event (both None without overlap)."""
-        spec, var = rec.spec, rec.var
-        dev = gy.device
-        ws = _Workspace.get(dev)
-        B, H, W = geo.B, geo.H, geo.W
-        C, cs_mid = spec.cout, cs_of(spec.cout)
-        x, cs_x, y, z = rec.x, rec.cs_x, rec.y, rec.z
-        pre = spec.prefix
-        sp = _lib.stream_ptr
-        packs = packs or {}
-        f16 = CONV_MODE == 'f16x3' and self.ksize == 2
-        bn = rec.bn                      # (False where a frozen evaluation folded BatchNorm into conv2: ReLU-only backward)
+    def _bn_bwd(self, tape, rec, bp, grads, g, dz):
+        """BatchNorm's part of a block's backward, as bp lists it: the batch sums with dgamma / dbeta (mmlf_bn_bwd_reduce), the
+        coefficients of dz, and dz itself, the gradient behind BatchNorm, written to the grid buffer `dz` (mmlf_bn_bwd_apply).
+        g: the gradient of the block's output.  Returns (dz as a _Slice or None, the coefficients: held by the caller)."""
+        geo, p, pre, C = tape.geo, tape.p, rec.spec.prefix, rec.spec.cout
+        cs_mid, sp, ws = cs_of(C), _lib.stream_ptr, _Workspace.get(tape.device)
+        g3w, g3b = (grads[f'{pre}.{k}'] if k in bp.want else None for k in ('3.weight', '3.bias'))
+        coef = None
+        if bp.reduce:
+            coef = torch.empty(3 * C, dtype=torch.float32, device=tape.device)
+            # an unwanted dgamma / dbeta goes to scratch: the batch sums still feed the coefficients (or the other of the two)
+            dgb = ws.scratch('bn_dgamma_dbeta', 2 * C) if g3w is None or g3b is None else None
+            dgamma, dbeta = (dgb[:C] if g3w is None else g3w), (dgb[C:2 * C] if g3b is None else g3b)
+            acc = int(g3w is not None or g3b is not None)
+            call('mmlf_bn_bwd_reduce', ptr(g.t), g.cs, g.off, ptr(rec.z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
+                 ptr(p[f'{pre}.3.weight']), ptr(rec.smean), ptr(rec.sinv), ptr(dgamma), ptr(dbeta), acc, ptr(coef),
+                 ptr(ws.partial), BN_BLOCKS, geo.B, geo.H, geo.W, sp())
+            if rec.eval and bp.apply:
+                coef[C:].zero_()        # no batch-statistics terms: dz = k1 * g (dgamma / dbeta sums are the same)
+        elif bp.apply:
+            # running statistics and nobody reads dgamma / dbeta: dz = k1 * g with k1 = gamma * invstd, formed as
+            # mmlf_bn_bwd_reduce forms it (the float64 product of gamma and the saved float32 invstd, rounded once), so that
+            # a frozen block hands down the bits the full backward does
+            assert rec.eval, (pre, bp)
+            coef = torch.zeros(3 * C, dtype=torch.float32, device=tape.device)
+            coef[:C].copy_((p[f'{pre}.3.weight'].double() * rec.sinv.double()).float())
+        if not bp.apply:
+            return None, coef
+        call('mmlf_bn_bwd_apply', ptr(g.t), g.cs, g.off, ptr(rec.z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
+             ptr(rec.smean), ptr(coef), ptr(dz), cs_mid, geo.B, geo.H, geo.W, ptr(dz.absmax), sp())
+        return _Slice(dz, cs_mid, 0), coef
+
+    def _block_bwd(self, tape, rec, bp, grads, g, side=None):
+        """g: the gradient w.r.t. the block output (_Slice; extent (H,W)).  Returns the gradient w.r.t. the block input
+        (_Slice) or None.  bp: the block's BlockPlan -- the launches that run, and nothing else decides one; grads holds the
+        tensors of bp.want.  The unwanted partner of a wanted tensor goes nowhere (gw / gb = NULL).  side (an out_net block):
+        the pass's _SideWgrad, settled once this block's BatchNorm-backward kernels are enqueued; a wide block's first weight
+        gradient goes to it behind the data gradient.  None (a stream block): all on the main stream, nothing is settled."""
+        if rec is None:
+            raise ValueError(f'Trunk.backward: the forward pass kept no record of {bp.prefix} (its trainable= / '
+                             'input_grads= did not ask for what this backward needs)')
+        spec, var, x, y, geo = rec.spec, rec.var, rec.x, rec.y, tape.geo
+        C, cs_mid, pre = spec.cout, cs_of(spec.cout), spec.prefix
         assert not bp.want or rec.pk2d is None, 'a frozen forward (BatchNorm folded) has no parameter gradients'
-        assert bool(bn) or not (bp.reduce or bp.apply), (pre, bp)
+        assert bool(rec.bn) or not (bp.reduce or bp.apply), (pre, bp)
         need_dx = bp.dgrad1
-        gw1, gb1, gw2, gb2, g3w, g3b = (grads[f'{pre}.{k}'] if k in bp.want else None
-                                        for k in ('0.weight', '0.bias', '2.weight', '2.bias', '3.weight', '3.bias'))
-
-        # the ReLU of y in conv2's data gradient: by the bits conv1's forward launch left, or else by y itself
-        y_relu = {'mask_in': rec.ymask} if rec.ymask is not None and f16 else {'ref': y, 'cs_ref': cs_mid}
-        # x is the output of a block without BatchNorm: the data gradient of conv1 applies that block's trailing ReLU, so what
-        # comes out is already the gradient behind it (dz of the block underneath) and costs no pass of its own.  In the f16
-        # split the mask comes as the bits the producing conv2 launch left: that launch and this one have the same (B, H, W),
-        # the same N (the block's width), out_shift P + 1 and a buffer of channel stride cs_x of their own, so they run the same
-        # kernel and epilogue orientation and agree on the private word layout.  Otherwise x itself is the reference.
-        x_relu = {}
-        if rec.x_relu:
-            x_relu = {'mask_in': rec.xmask} if rec.xmask is not None and f16 else {'ref': x, 'cs_ref': cs_x}
-
+        gw1, gb1, gw2, gb2 = (grads[f'{pre}.{k}'] if k in bp.want else None for k in ('0.weight', '0.bias', '2.weight', '2.bias'))
+        conv1, conv2 = _Filter(False, spec.cin, C, var), _Filter(True, C, C, var)
         # this block's gradient buffers, one zeroing launch: dz (behind BatchNorm), dy, dx
-        css = ([cs_mid] if bp.apply else []) + ([cs_mid] if bp.dgrad2 else []) + ([cs_x] if need_dx else [])
-        got = geo.bufs(css, dev) if css else []
-        dy = got[1 if bp.apply else 0] if bp.dgrad2 else None
-        dx = got[-1] if need_dx else None
-        dz = None
-        if bn:
-            if bp.reduce:
-                coef = torch.empty(3 * C, dtype=torch.float32, device=dev)
-                # an unwanted dgamma / dbeta goes to scratch: the batch sums still feed the coefficients (or the other of the two)
-                dgb = ws.scratch('bn_dgamma_dbeta', 2 * C) if g3w is None or g3b is None else None
-                dgamma, dbeta = (dgb[:C] if g3w is None else g3w), (dgb[C:2 * C] if g3b is None else g3b)
-                acc = int(g3w is not None or g3b is not None)
-                call('mmlf_bn_bwd_reduce', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
-                     ptr(p[f'{pre}.3.weight']), ptr(rec.smean), ptr(rec.sinv), ptr(dgamma), ptr(dbeta), acc, ptr(coef),
-                     ptr(ws.partial), BN_BLOCKS, B, H, W, sp())
-                if rec.eval and bp.apply:
-                    coef[C:].zero_()        # no batch-statistics terms: dz = k1 * g (dgamma / dbeta sums are the same)
-            elif bp.apply:
-                # running statistics and nobody reads dgamma / dbeta: dz = k1 * g with k1 = gamma * invstd, formed as
-                # mmlf_bn_bwd_reduce forms it (the float64 product of gamma and the saved float32 invstd, rounded once), so that
-                # a frozen block hands down the bits the full backward does
-                assert rec.eval, (pre, bp)
-                coef = torch.zeros(3 * C, dtype=torch.float32, device=dev)
-                coef[:C].copy_((p[f'{pre}.3.weight'].double() * rec.sinv.double()).float())
-            if bp.apply:
-                dz = got[0]
-                call('mmlf_bn_bwd_apply', ptr(gy), cs_gy, c_off, ptr(z), cs_mid, C, ptr(rec.scale), ptr(rec.shift),
-                     ptr(rec.smean), ptr(coef), ptr(dz), cs_mid, B, H, W, ptr(dz.absmax), sp())
+        css = ([cs_mid] if bp.apply else []) + ([cs_mid] if bp.dgrad2 else []) + ([x.cs] if need_dx else [])
+        got = geo.bufs(css, tape.device) if css else []
+        dy = _Slice(got[1 if bp.apply else 0], cs_mid, 0) if bp.dgrad2 else None
+        dx = _Slice(got[-1], x.cs, 0) if need_dx else None
+        if rec.bn:         # (False where a frozen evaluation folded BatchNorm into conv2: ReLU-only backward)
+            dz, coef = self._bn_bwd(tape, rec, bp, grads, g, got[0] if bp.apply else None)   # (coef: held until the return)
         else:
-            assert c_off == 0 and cs_gy == cs_mid
-            dz = gy
-        if after_bn:
-            after_bn()
+            assert g.off == 0 and g.cs == cs_mid
+            dz = g
+        if side is not None:
+            side.settle()
         # conv2: weight / bias gradient, then data gradient fused with the ReLU of y
         if bp.wgrad2:
-            self._wgrad(geo, True, y, cs_mid, C, dz, cs_mid, C, gw2, gb2, var)
+            self._wgrad(geo, conv2, y, dz, (gw2, gb2))
         if bp.dgrad2:
-            pk2d = rec.pk2d if rec.pk2d is not None else self._packed(packs, p, f'{pre}.2.weight', var, True)
-            self._dgrad(geo, True, dz, cs_mid, C, pk2d, C, dy, cs_mid, **y_relu)
+            pk2d = rec.pk2d if rec.pk2d is not None else self._packed(tape, f'{pre}.2.weight', var, True)
+            self._dgrad(geo, dz, conv2._replace(packed=pk2d), dy, y)
         del dz, got
-        # conv1: the same, with the ReLU (if any) of the block underneath
-        if overlap and need_dx and bp.wgrad1:
-            self._dgrad(geo, False, dy, cs_mid, C, self._packed(packs, p, f'{pre}.0.weight', var, True), spec.cin, dx, cs_x,
-                        **x_relu)
-            main = torch.cuda.current_stream()
-            ready = main.record_event()
-            with torch.cuda.stream(ws.side):
-                ws.side.wait_event(ready)
-                self._wgrad(geo, False, x, cs_x, spec.cin, dy, cs_mid, C, gw1, gb1, var, side=True)
-                done = ws.side.record_event()
-            # x and dy are read by the side stream: the caller keeps them alive until the main stream has waited
-            # for `done` (no record_stream: deferred reuse makes the caching allocator grow and stall)
-            return dx, done, (x, dy)
-        if bp.wgrad1:
-            self._wgrad(geo, False, x, cs_x, spec.cin, dy, cs_mid, C, gw1, gb1, var)
+        # conv1: the same, with the ReLU (if any) of the block underneath: x is then the output of a block without BatchNorm,
+        # and what comes out is already the gradient behind that block's trailing ReLU (its dz) at no pass of its own
+        overlap = side is not None and side.takes(spec.cin) and need_dx and bp.wgrad1
+        if bp.wgrad1 and not overlap:
+            self._wgrad(geo, conv1, x, dy, (gw1, gb1))
         if need_dx:
-            self._dgrad(geo, False, dy, cs_mid, C, self._packed(packs, p, f'{pre}.0.weight', var, True), spec.cin, dx, cs_x,
-                        **x_relu)
-        return dx, None, None
+            self._dgrad(geo, dy, conv1._replace(packed=self._packed(tape, f'{pre}.0.weight', var, True)), dx, x)
+        if overlap:
+            side.launch(pre, (x.t, dy.t), lambda: self._wgrad(geo, conv1, x, dy, (gw1, gb1), side=True))
+        elif side is not None:
+            side.kept = None                         # (no launch of this block's: the last launch's tensors go, see launch())
+        return dx
 
     def backward(self, p, tape, grad_output, grads, on_done=None, input_grads=None):
         """grad_output: (B,oc,H,W) NCHW.  grads: dict name -> tensor, ACCUMULATED into
@@ -1009,94 +1044,59 @@ class Trunk:
         launch nothing, as soon as nothing more can come for it (gradient-bucket all-reduce hook).
         input_grads: four bools (streams H, V, I, D), the view stacks whose gradient is wanted; default none.  Returns a list
         of four entries: the (B, views, 3, H, W) float32 gradient of a wanted stack, None for the others.  The parameter
-        gradients do not depend on it: the same weight-gradient launches in the same order."""
-        geo, dev = tape['geo'], tape['device']
+        gradients do not depend on it: the same weight-gradient launches in the same order.  The tape is used up: a block's
+        record is released as soon as its launches are enqueued, the concat buffer at the end."""
+        geo, dev = tape.geo, tape.device
         check(grad_output, 'grad_output', dev, shape=(geo.B, self.oc, geo.H, geo.W), contiguous=False)
-        fplan = tape.get('plan')
+        fplan = tape.plan
         if grads is not None:
             wanted = self._grad_names if fplan is None else [n for n in self._grad_names if n in fplan.trainable]
             self._check_dict('grads', grads, wanted, dev)
-        _Workspace.get(dev).enter_stream()
+        ws = _Workspace.get(dev)
+        ws.enter_stream()
         B, H, W = geo.B, geo.H, geo.W
-        cs = cs_of(self.oc)
-        g = geo.buf(cs, dev)
-        call('mmlf_pack_nchw', ptr(grad_output.contiguous()), self.oc, ptr(g), cs, B, H, W, ptr(g.absmax),
+        g = _Slice(geo.buf(cs_of(self.oc), dev), cs_of(self.oc), 0)
+        call('mmlf_pack_nchw', ptr(grad_output.contiguous()), self.oc, ptr(g.t), g.cs, B, H, W, ptr(g.t.absmax),
              _lib.stream_ptr())
-        cs_g = cs
         want = [bool(w) for w in input_grads] if input_grads is not None else [False] * 4
         assert len(want) == 4
         # this pass's plan: the forward's wanted names (none with grads=None) and the stacks asked for HERE; it may ask for
         # less than the forward recorded for, never for more
         bplan = self.plan(fplan.trainable if grads is not None else (), want, fplan.train, fplan.fold)
-
-        def rec_for(rec, bp):
-            if rec is None:
-                raise ValueError(f'Trunk.backward: the forward pass kept no record of {bp.prefix} (its trainable= / '
-                                 'input_grads= did not ask for what this backward needs)')
-            return rec
+        tape.p = p
+        side =_SideWgrad(ws, on_done, OVERLAP_WGRAD and self.ksize == 2)
         dstacks = [None] * 4
-        recs = tape['out']
-        main = torch.cuda.current_stream()
-        pending = None                      # (event, prefix, tensors) of a weight gradient still running on the side stream
-
-        def settle():
-            nonlocal pending
-            if pending is not None:
-                main.wait_event(pending[0])
-                if on_done:
-                    on_done(pending[1])
-                pending = None              # drops the tensors the side stream was reading
-
-        while recs:
-            rec = recs.pop()
-            bp = bplan.out[len(recs)]
-            if bp is None:
-                # the block and everything beneath it launch nothing: its key is complete as soon as the block above is
-                g = None
-                settle()
-                if on_done:
-                    on_done(self.out_blocks[len(recs)].prefix)
+        for site in reversed(self.sites):
+            rec, tape.recs[site.index] = tape.recs[site.index], None
+            bp, s = bplan.of(site), site.chain
+            if s == 4:
+                if bp is None:
+                    # the block and everything beneath it launch nothing: its key is complete as soon as the block above is
+                    g = None
+                    side.settle()
+                else:
+                    g = self._block_bwd(tape, rec, bp, grads, g, side)
+                side.done(site.spec.prefix)
                 continue
-            rec = rec_for(rec, bp)
-            # (layers wider than one launch run their weight gradient as column blocks, the second of them on kernels the
-            # register budget of the overlap was not drawn up for: they stay on the main stream, DESIGN.md 4.14)
-            wide = OVERLAP_WGRAD and 128 <= rec.spec.cin <= MAX_OVERLAP_WIDTH and self.ksize == 2
-            g, event, keep = self._block_bwd(geo, rec, bp, p, grads, g, cs_g, 0, after_bn=settle, overlap=wide,
-                                             packs=tape['packs'])
-            settle()                        # (blocks without BatchNorm never called it)
-            if event is not None:
-                pending = (event, rec.spec.prefix, keep)
-            elif on_done:
-                on_done(rec.spec.prefix)
-            cs_g = rec.cs_x
-        # g is now the gradient w.r.t. the concat buffer (cs = 4*chs); streams read channel slices
-        for s in reversed(range(4)):
-            recs = tape['streams'][s]
-            if s == 2:
-                settle()                    # out_net.0's weight gradient ran beside the first stream's BatchNorm kernels
-            if not bplan.stream_live[s]:
-                del recs[:]                 # a stream without a live block is skipped, its ReLU slice included
-            gs, cs_s, off = g, cs_g, s * self.chs
-            if bplan.slices[s]:
-                if 'concat' not in tape:
-                    raise ValueError('Trunk.backward: the forward pass kept no concat buffer for this backward')
-                # the stream's last ReLU wrote its slice of the concat buffer: the gradient behind it, as a compact tensor
-                cs_s, off = cs_of(self.chs), 0
-                gs = geo.buf(cs_s, dev)
-                relu_bwd_slice(geo, g, cs_g, s * self.chs, tape['concat'], cs_g, s * self.chs, self.chs, gs, cs_s)
-            while recs:
-                rec = recs.pop()
-                bp = bplan.streams[s][len(recs)]
-                if bp is None:              # (live blocks sit on top of a chain: nothing beneath this one runs either)
-                    del recs[:]
-                    break
-                rec = rec_for(rec, bp)
-                gs, _, _ = self._block_bwd(geo, rec, bp, p, grads, gs, cs_s, off, packs=tape['packs'])
-                cs_s, off = rec.cs_x, 0
-            if want[s]:
-                # gs: the gradient of the stream's packed input, extent (H, W) at (1, 1), 3 views channels of cs_s
-                dstacks[s] = torch.empty((B, self.views, 3, H, W), dtype=torch.float32, device=dev)
-                call('mmlf_unpack_nchw', ptr(gs), cs_s, ptr(dstacks[s]), 3 * self.views, B, H, W, _lib.stream_ptr())
-            if on_done and s in (2, 0):      # shared stream nets: complete after the I (resp. H) stream
-                on_done('in_net_id' if s == 2 else 'in_net_hv')
+            if site.last:
+                # g is the gradient w.r.t. the concat buffer (cs = 4*chs); a stream reads its channel slice
+                if s == 2:
+                    side.settle()            # (out_net.0's weight gradient ran beside the D stream's BatchNorm kernels)
+                gs = None if g is None else _Slice(g.t, g.cs, s * self.chs)
+                if bplan.slices[s]:
+                    if tape.concat is None:
+                        raise ValueError('Trunk.backward: the forward pass kept no concat buffer for this backward')
+                    # the stream's last ReLU wrote its slice of the concat buffer: the gradient behind it, as a compact tensor
+                    gs = _Slice(geo.buf(cs_of(self.chs), dev), cs_of(self.chs), 0)
+                    relu_bwd_slice(geo, g.t, g.cs, s * self.chs, tape.concat, g.cs, s * self.chs, self.chs, gs.t, gs.cs)
+            if bp is not None:               # (live blocks sit on top of a chain: nothing beneath a block without a plan runs)
+                gs = self._block_bwd(tape, rec, bp, grads, gs)
+            if site.k == 0:
+                if want[s]:
+                    # gs: the gradient of the stream's packed input, extent (H, W) at (1, 1), 3 views channels of gs.cs
+                    dstacks[s] = torch.empty((B, self.views, 3, H, W), dtype=torch.float32, device=dev)
+                    call('mmlf_unpack_nchw', ptr(gs.t), gs.cs, ptr(dstacks[s]), 3 * self.views, B, H, W, _lib.stream_ptr())
+                if s in (2, 0):              # shared stream nets: complete after the I (resp. H) stream
+                    side.done('in_net_id' if s == 2 else 'in_net_hv')
+        tape.concat = None
         return dstacks

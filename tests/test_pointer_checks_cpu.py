@@ -173,7 +173,8 @@ def test_a_validated_model_is_checked_again_when_a_tensor_changes():
 
 # ------------------------------------------------------------------ Trunk.backward
 def _tape():
-    return {'geo': _geo(), 'device': CPU}
+    from mmlf_amd.engine import _Tape
+    return _Tape(_geo(), CPU)
 
 
 @pytest.mark.parametrize('gout', [torch.zeros(B, 1, H, W + 1), torch.zeros(B, 2, H, W), torch.zeros(B, 1, H, W).double(),

@@ -1,6 +1,36 @@
 """Small numpy helpers shared by the GPU parity tests."""
+import contextlib
+
 import numpy as np
 import torch
+
+
+@contextlib.contextmanager
+def dry_engine(extents=False, mode='f16x3'):
+    """The host code of mmlf_amd.engine without a GPU, as `tools/launch_trace.py --dry` runs it: engine.call records
+    (name, args) into the list this yields and launches nothing (the host-only mmlf_audit_* entries still run), the stream
+    pointer is 0, the side-stream weight gradient is off.  The caller keeps its tensors on the CPU.  extents:
+    MMLF_CHECK_EXTENTS, with engine.EXTENT_CHECKS reset to 0."""
+    from mmlf_amd import _lib, engine
+    calls = []
+    real = engine.call
+
+    def record(name, *args):
+        calls.append((name, args))
+        if name.startswith('mmlf_audit_'):
+            real(name, *args)
+
+    names = ('call', 'CONV_MODE', 'OVERLAP_WGRAD', 'CHECK_EXTENTS', 'EXTENT_CHECKS')
+    saved, stream_ptr = [getattr(engine, n) for n in names], _lib.stream_ptr
+    engine.call, engine.CONV_MODE, engine.OVERLAP_WGRAD, engine.CHECK_EXTENTS, engine.EXTENT_CHECKS = record, mode, False, extents, 0
+    _lib.stream_ptr = lambda: 0
+    try:
+        yield calls
+    finally:
+        _lib.stream_ptr = stream_ptr
+        for n, v in zip(names, saved):
+            if n != 'EXTENT_CHECKS':             # (the count stays readable behind the block)
+                setattr(engine, n, v)
 
 
 def _master(dy, dx, variant):
