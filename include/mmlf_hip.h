@@ -208,6 +208,8 @@ int mmlf_conv2x2_wgrad_h2(const float *in, int cs_in, int Cin, const float *g, i
 /* nn.BatchNorm2d training statistics (feed_forward.py:134): per-channel mean / biased variance of
  * the extent-(H,W) tensor z (zero border), running-stat update (unbiased var), and the affine
  * coefficients scale = gamma*invstd, shift = beta - mean*scale.  partial: 2*C*nblocks doubles.
+ * running_mean / running_var may be NULL (both of them; running_mean decides): save_mean, save_invstd, scale and shift
+ * are formed as with buffers and no running statistic is read or written (a later micro-batch of a train step).
  * refuses: cs % 4, C outside [1, min(cs, 1024)], nblocks outside [1, 4096], B, H or W < 1. */
 int mmlf_bn_stats_train(const float *z, int cs, int C, const float *gamma, const float *beta,
                         float *running_mean, float *running_var, double momentum, double eps,
@@ -226,6 +228,7 @@ int mmlf_fold_bn_eval(const float *w_oihw, const float *bias, const float *scale
  * mmlf_conv2x2_h2(bn_partial = partial) writes per-workgroup sums of z and z^2 per channel
  * ([mmlf_conv2x2_blocks()][2][C] doubles) from its epilogue, so the pad-0 convolution's output is not
  * read again for nn.BatchNorm2d's training statistics (feed_forward.py:134).
+ * running_mean / running_var may be NULL, as for mmlf_bn_stats_train: the statistics and coefficients alone.
  * refuses: C < 1, nblocks < 1, B, H or W < 1. */
 int mmlf_bn_stats_finalize(const double *partial, int nblocks, int C, const float *gamma, const float *beta,
                            float *running_mean, float *running_var, double momentum, double eps,

@@ -475,13 +475,14 @@ class _Rec:
 
 class _Tape:
     """One pass over the trunk: what its blocks share and what forward leaves for backward (Trunk.forward returns it).  plan:
-    the forward's Plan (None: nothing is saved); packs: the step's prepacked filters; tracked: the BatchNorm counters the pass
-    moves; deferred: (z, scale, shift) of the streams' last blocks, whose BatchNorm-apply runs as ONE pass (None: each block
+    the forward's Plan (None: nothing is saved); packs: the step's prepacked filters; running: a train-mode pass moves
+    BatchNorm's running statistics and counters (False: a later micro-batch of a step); tracked: the counters the pass moves;
+    deferred: (z, scale, shift) of the streams' last blocks, whose BatchNorm-apply runs as ONE pass (None: each block
     applies its own); concat: kept behind forward for mmlf_relu_bwd_slice only; recs[site.index]: a live block's record."""
-    __slots__ = ('geo', 'device', 'p', 'train', 'fold', 'plan', 'packs', 'tracked', 'deferred', 'concat', 'recs')
+    __slots__ = ('geo', 'device', 'p', 'train', 'fold', 'plan', 'packs', 'running', 'tracked', 'deferred', 'concat', 'recs')
 
-    def __init__(self, geo, device, p=None, train=False, fold=False, plan=None, packs=None, sites=0):
-        self.geo, self.device, self.p, self.train, self.fold, self.plan = geo, device, p, train, fold, plan
+    def __init__(self, geo, device, p=None, train=False, fold=False, plan=None, packs=None, sites=0, running=True):
+        self.geo, self.device, self.p, self.train, self.fold, self.plan, self.running = geo, device, p, train, fold, plan, running
         self.packs, self.tracked, self.deferred, self.concat, self.recs = packs or {}, [], None, None, [None] * sites
 
 
@@ -780,7 +781,8 @@ class Trunk:
     # ------------------------------------------------------------------ forward
     def _bn_fwd(self, tape, spec, z, rec):
         """(scale, shift, smean, sinv) of a block's BatchNorm.  Train mode: the batch statistics of z (conv2's output) --
-        from the sums conv2's epilogue left (f16 split) or a pass over z -- which also move the running statistics; eval
+        from the sums conv2's epilogue left (f16 split) or a pass over z -- which also move the running statistics (unless
+        tape.running is False: NULL running pointers, the statistics and coefficients alone, no counter tracked); eval
         mode: the running statistics' coefficients, and under a tape (rec: the block's record) the statistics themselves.
         z None: the eval coefficients alone, for the fold into conv2 (smean, sinv: None)."""
         geo, p, pre, C, sp = tape.geo, tape.p, spec.prefix, spec.cout, _lib.stream_ptr
@@ -790,14 +792,16 @@ class Trunk:
         g, bt, rm, rv = (p[f'{pre}.3.{k}'] for k in ('weight', 'bias', 'running_mean', 'running_var'))
         if tape.train:
             partial = _Workspace.get(tape.device).partial
+            moved = (rm, rv) if tape.running else (None, None)
             if self._f16():
                 nblk = int(_lib.load().mmlf_conv2x2_blocks(C, C, geo.B, geo.H, geo.W))
-                call('mmlf_bn_stats_finalize', ptr(partial), nblk, C, ptr(g), ptr(bt), ptr(rm), ptr(rv),
+                call('mmlf_bn_stats_finalize', ptr(partial), nblk, C, ptr(g), ptr(bt), ptr(moved[0]), ptr(moved[1]),
                      self.momentum, self.eps, ptr(smean), ptr(sinv), ptr(scale), ptr(shift), geo.B, geo.H, geo.W, sp())
             else:
-                call('mmlf_bn_stats_train', ptr(z), cs_of(C), C, ptr(g), ptr(bt), ptr(rm), ptr(rv), self.momentum,
+                call('mmlf_bn_stats_train', ptr(z), cs_of(C), C, ptr(g), ptr(bt), ptr(moved[0]), ptr(moved[1]), self.momentum,
                      self.eps, ptr(smean), ptr(sinv), ptr(scale), ptr(shift), ptr(partial), BN_BLOCKS, geo.B, geo.H, geo.W, sp())
-            tape.tracked.append(p[f'{pre}.3.num_batches_tracked'])
+            if tape.running:
+                tape.tracked.append(p[f'{pre}.3.num_batches_tracked'])
         else:
             call('mmlf_bn_coeffs_eval', ptr(g), ptr(bt), ptr(rm), ptr(rv), self.eps, ptr(scale), ptr(shift), C, sp())
             if rec is not None:
@@ -873,7 +877,8 @@ class Trunk:
                  dest.cs if new_out else C, geo.B, geo.H, geo.W, ptr(dest.t.absmax), _lib.stream_ptr())
         return _Act(dest.t, dest.cs, False, None)
 
-    def forward(self, p, stacks, train, save, packed=None, input_grads=None, frozen=False, trainable=None):
+    def forward(self, p, stacks, train, save, packed=None, input_grads=None, frozen=False, trainable=None,
+                update_running=True, packs=None):
         """stacks: four (B, views, 3, H, W) contiguous float32 device tensors.  They, the grid tensors of `packed` and every
         entry of `p` the blocks read are validated here (_lib.check), ahead of the first call into the library.
         packed (instead of stacks): (Geometry, [four grid tensors of channel stride cs_of(3 views), with their amax arrays]) --
@@ -887,6 +892,12 @@ class Trunk:
         the empty set).  Together with input_grads it makes the step's plan (Trunk.plan): blocks that are not live leave no
         record and write no ReLU bits, the concat buffer is kept only for a live stream, and only the planned data gradients'
         filter forms are packed.  BatchNorm's running statistics move in train mode whatever is frozen, as in torch.
+        update_running (train mode): False leaves every BatchNorm buffer -- running statistics and counters -- untouched; the
+        batch statistics and the coefficients are formed as ever (a later micro-batch of a train step: device 0's buffers
+        persist under nn.DataParallel).  Eval mode reads the running statistics whatever it says.
+        packs: the `packs` of an earlier pass's tape, used instead of packing the filters again.  The caller vouches that
+        nothing has changed since that pass: the weights, the plan (train, trainable, input_grads, frozen), the thread and the
+        stream (_Workspace.packed_filters: the store behind the views is overwritten by the next packing launch).
         Returns (output NCHW (B,oc,H,W), tape or None)."""
         cin0 = self.views * 3
         if packed is not None:
@@ -913,7 +924,8 @@ class Trunk:
         # have no ReLU-only backward and keep the unfolded form under a tape)
         plan = self.plan(() if frozen else trainable, input_grads, train) if save else None
         fold = self.batchnorm and not train and (not save or plan.fold)
-        tape = _Tape(geo, dev, p, train, fold, plan, self._prepack(p, dev, plan, fold), len(self.sites))
+        tape = _Tape(geo, dev, p, train, fold, plan, self._prepack(p, dev, plan, fold) if packs is None else packs,
+                     len(self.sites), bool(update_running))
         cs_in, cs_cat = cs_of(cin0), 4 * self.chs
         if packed is not None:
             tape.concat, xs = geo.buf(cs_cat, dev), list(xs_in)

@@ -96,12 +96,13 @@ def native_multi_loss(kind, output, target, mask, mask_padding=None, grid_torch=
 
 
 class _NativeMultiLossFn(torch.autograd.Function):
-    """autograd node of the multimodal / padded losses for callers that go through the loss modules"""
+    """autograd node of the multimodal / padded losses for callers that go through the loss modules.  aux: the kernel's
+    aux_override (a micro-batch of a train step hands in the whole batch's sums), None: the tensor's own sums"""
 
     @staticmethod
-    def forward(ctx, kind, target, mask, mask_padding, *heads):
+    def forward(ctx, kind, target, mask, mask_padding, aux, *heads):
         out = torch.stack(list(heads), 1)
-        loss, grad = native_multi_loss(kind, out.detach(), target, mask, mask_padding)
+        loss, grad = native_multi_loss(kind, out.detach(), target, mask, mask_padding, aux_override=aux)
         ctx.save_for_backward(grad)
         return loss
 
@@ -109,7 +110,7 @@ class _NativeMultiLossFn(torch.autograd.Function):
     def backward(ctx, gl):
         (grad,) = ctx.saved_tensors
         g = grad * gl
-        return (None, None, None, None) + tuple(g[:, k] for k in range(g.shape[1]))
+        return (None, None, None, None, None) + tuple(g[:, k] for k in range(g.shape[1]))
 
 
 class _NativeLossFn(torch.autograd.Function):
@@ -184,7 +185,7 @@ class ImprovedUncertaintyL1Loss(nn.Module):
         if mean.is_cuda and mask_padding is None:
             return _NativeLossFn.apply(KIND_UPR, target, mask, None, 0.0, mean, logvar)
         if mean.is_cuda:
-            return _NativeMultiLossFn.apply(KIND_UPR_PADDED, target, mask, mask_padding, mean, logvar)
+            return _NativeMultiLossFn.apply(KIND_UPR_PADDED, target, mask, mask_padding, None, mean, logvar)
         loss = torch.exp(-logvar) * torch.abs(mean - target) + logvar
         if mask_padding is not None:
             mp = mask_padding.float()
@@ -216,7 +217,7 @@ class MultiMaskedL1Loss(nn.Module):
 
     def forward(self, input, target, mask):
         if input['mean'].is_cuda:
-            return _NativeMultiLossFn.apply(KIND_MULTI_L1, target, mask, None, input['mean'])
+            return _NativeMultiLossFn.apply(KIND_MULTI_L1, target, mask, None, None, input['mean'])
         weights, targets = target[:, :, 3], target[:, :, 4]
         diff = (torch.abs(input['mean'].unsqueeze(1) - targets) * weights).sum(1)
         return _masked_mean(diff, mask)
@@ -229,7 +230,7 @@ class ImprovedMultiUncertaintyL1Loss(nn.Module):
     def forward(self, input, target, mask, mask_padding=None):
         mean, logvar = input['mean'], input['logvar']
         if mean.is_cuda:
-            return _NativeMultiLossFn.apply(KIND_MULTI_UPR, target, mask, None, mean, logvar)
+            return _NativeMultiLossFn.apply(KIND_MULTI_UPR, target, mask, None, None, mean, logvar)
         weights, targets = target[:, :, 3], target[:, :, 4]
         loss = torch.exp(-logvar).unsqueeze(1) * torch.abs(mean.unsqueeze(1) - targets) + logvar.unsqueeze(1)
         total = weights.sum(1)

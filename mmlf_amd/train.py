@@ -9,11 +9,15 @@ rank trains on its shard of the batch with replica-local BatchNorm statistics (a
 replicas do), and ONE sum all-reduce of the flat float32 gradient crosses xGMI per step, issued per
 bucket as soon as backward has produced it (RCCL: backend "nccl"; gloo on CPU for tests).
 
+``TrainStep(micro_batches=n)`` runs the same n-replica step in ONE process: the batch in DataParallel's n chunks, one pass per
+chunk, gradients accumulated, one Adam step; it composes with the data parallelism above.
+
 On CUDA tensors everything between the input stacks and the updated parameters runs in HIP kernels
 (engine.Trunk, mmlf_loss_fwd_bwd, mmlf_adam_step); on CPU tensors (gloo rehearsal, CPU tests) the
 module's torch plumbing path + autograd + the same flat Adam arithmetic in torch ops is used.
 """
 import math
+import operator
 
 import torch
 import torch.distributed as dist
@@ -176,11 +180,51 @@ class GradBuckets:
         self.pending, self.done = [], set()
 
 
+class _Chunks:
+    """What the micro-batches of one step share (TrainStep._chunked_fwd_bwd).  index / count: the chunk that runs now; den:
+    the whole batch's loss denominator (under data parallelism first the pending all-reduce that chunk 0 waits for behind its
+    forward pass); aux: the whole batch's sums the multimodal UPR / padded UPR losses normalise by (over all ranks), None for
+    the other losses; pixels: B * H * W of the whole batch, over all ranks; mp: the padded UPR loss's in-range masks, one per
+    chunk; packs: the step's packed filters, made by chunk 0's forward pass (the weights do not change inside a step)."""
+    __slots__ = ('index', 'count', 'den', 'aux', 'pixels', 'mp', 'packs', '_scaled')
+
+    def __init__(self, count, den, aux, pixels, mp):
+        self.index, self.count, self.den, self.aux, self.pixels, self.mp = 0, count, den, aux, pixels, mp
+        self.packs, self._scaled = None, {}
+
+    def first(self):
+        return self.index == 0
+
+    def last(self):
+        return self.index == self.count - 1
+
+    def chunk_aux(self, n):
+        """the whole-batch sums scaled by a chunk's share n / pixels of the pixels: the loss kernel forms aux[0] / n and
+        n / aux[1] from its own n (TrainStep._scaled_aux does the same per rank).  Product first: a sum that equals `pixels`
+        (every pixel in range) comes out as n exactly.  At most two chunk sizes occur in a step."""
+        if self.aux is None:
+            return None
+        if n not in self._scaled:
+            self._scaled[n] = self.aux * n / self.pixels
+        return self._scaled[n]
+
+
 class TrainStep:
     def __init__(self, model, lr, variant=None, warm_start=False, cooling=0, betas=(0.9, 0.999), eps=1e-8,
                  loss_margin=11, process_group=None, loss_multimodal=False, loss_padding=None,
-                 train_eval_mode=False, train_eval_mode_start=0, loss_strongest=False, force_distributed=False):
+                 train_eval_mode=False, train_eval_mode_start=0, loss_strongest=False, force_distributed=False,
+                 micro_batches=1):
         self.model = model
+        # micro_batches = n: a step takes its batch through the net as nn.DataParallel's scatter cuts it for n devices
+        # (Tensor.chunk(n): ceil(B / n) samples each, maybe fewer than n, the last maybe shorter), one forward + backward pass
+        # per chunk, gradients accumulated, ONE Adam step: the reference's 8-replica step (train/cli.py:159) in one process, at
+        # the activation memory of one chunk.  _chunked_fwd_bwd has the semantics.
+        try:
+            self.micro_batches = operator.index(micro_batches)
+        except TypeError:
+            raise ValueError(f'TrainStep: micro_batches must be an integer >= 1, got {micro_batches!r}') from None
+        if self.micro_batches < 1:
+            raise ValueError(f'TrainStep: micro_batches must be an integer >= 1, got {micro_batches!r}')
         # --train_eval_mode / --train_eval_mode_start (train/cli.py:227-230): BatchNorm uses its running statistics
         self.eval_mode, self.eval_mode_start = bool(train_eval_mode), int(train_eval_mode_start)
         self.lr, self.warm_start, self.cooling = float(lr), bool(warm_start), int(cooling)
@@ -295,24 +339,78 @@ class TrainStep:
         mask = self._mask(mask)
         den = self._den_begin(mask)
         self.grad.zero_()
-        if h.is_cuda and model._native_ok:
-            loss = self._native_fwd_bwd(h, v, i_, d, gt, mask, den)
+        fwd_bwd = self._native_fwd_bwd if h.is_cuda and model._native_ok else self._torch_fwd_bwd
+        chunks = self._split(h, v, i_, d, gt, mask)
+        if chunks is None:
+            loss = fwd_bwd(h, v, i_, d, gt, mask, den)
         else:
-            loss = self._torch_fwd_bwd(h, v, i_, d, gt, mask, den)
+            loss = self._chunked_fwd_bwd(fwd_bwd, chunks, gt, mask, den)
         if self.distributed:
             self.buckets.finish(self.grad)
         self.adam_steps += 1
         self._adam(lr, 1.0 / self.world)
         return loss
 
-    def _native_fwd_bwd(self, h, v, i_, d, gt, mask, den):
+    def _split(self, *tensors):
+        """The step's tensors cut along the batch axis as nn.DataParallel's scatter cuts them for `micro_batches` devices:
+        one tuple of views per chunk (nothing is copied).  None where the step is a single pass: micro_batches = 1, or a batch
+        that makes one chunk -- the step then runs exactly the launches of a TrainStep without the argument."""
+        if self.micro_batches == 1:
+            return None
+        parts = [t.chunk(self.micro_batches) for t in tensors]
+        if len(parts[0]) == 1:
+            return None
+        assert all(len(part) == len(parts[0]) for part in parts), [t.shape[0] for t in tensors]
+        return list(zip(*parts))
+
+    def _chunked_fwd_bwd(self, fwd_bwd, chunks, gt, mask, den):
+        """The reference's nn.DataParallel step (train/cli.py:159,243-258) over the chunks of this rank's batch, one after the
+        other: every chunk is a replica with its own BatchNorm batch statistics, the loss is the masked mean over the WHOLE batch
+        (every chunk is normalised by the whole batch's valid-pixel count and, for the multimodal UPR / padded UPR losses, by the
+        whole batch's sums -- all formed once, here, ahead of chunk 0), the gradients are summed in self.grad, and the BatchNorm
+        buffers move by chunk 0's forward pass only (device 0's buffers persist).  Under data parallelism the counts are the
+        global ones (`den` is _den_begin's pending all-reduce, which chunk 0 waits for behind its forward pass) and the bucket
+        hooks belong to the last chunk's backward: nothing is all-reduced before every chunk has accumulated.
+        fwd_bwd: _native_fwd_bwd or _torch_fwd_bwd; gt, mask: the whole batch's.  Returns the sum of the chunks' losses, which
+        is this rank's whole-batch loss."""
+        if den is None:
+            den = mask.sum().double().reshape(1)
+        aux, mp = None, None
+        if self.variant == 'upr' and self.multimodal:
+            alpha = gt[:, :, 3]
+            if self.loss_padding is not None:             # (_padded_mpi's alpha, without a copy of the other planes)
+                alpha = alpha * (torch.abs(gt[:, :, 4]) < self.loss_padding).float()
+            aux = self._aux_sums(loss_mod.KIND_MULTI_UPR, alpha.sum(1), None)
+        elif self.variant == 'upr' and self.loss_padding is not None:
+            whole = (torch.abs(gt) < self.loss_padding).int()
+            aux, mp = self._aux_sums(loss_mod.KIND_UPR_PADDED, None, whole), whole.chunk(self.micro_batches)
+        share = _Chunks(len(chunks), den, aux, mask.numel() * self.world, mp)
+        losses, saved = [], None
+        buffers = list(self.model.buffers()) if fwd_bwd == self._torch_fwd_bwd and self.model.training else []
+        for k, chunk in enumerate(chunks):
+            share.index = k
+            losses.append(fwd_bwd(*chunk, share.den, share))
+            if buffers:        # the stock modules move their buffers in every pass: chunk 0's stay
+                with torch.no_grad():
+                    if saved is None:
+                        saved = [b.clone() for b in buffers]
+                    else:
+                        torch._foreach_copy_(buffers, saved)
+        return torch.stack(losses).sum()
+
+    def _native_fwd_bwd(self, h, v, i_, d, gt, mask, den, share=None):
+        """share: this pass is a chunk of a step (_Chunks), None: the whole step.  Chunk 0 moves BatchNorm's running statistics
+        and packs the step's filters; the last chunk's backward carries the bucket hooks."""
         model = self.model
         p = model._tensor_dict()
         with torch.no_grad():
-            out, tape = model._trunk.forward(p, [h, v, i_, d], model.training, True, trainable=self.trainable)
+            extra = {} if share is None else {'update_running': share.first(), 'packs': share.packs}
+            out, tape = model._trunk.forward(p, [h, v, i_, d], model.training, True, trainable=self.trainable, **extra)
             den = self._den_end(den)
+            if share is not None:
+                share.den, share.packs = den, tape.packs
             if self.multimodal:
-                loss, gout = self._multimodal_loss(out, gt, mask, den)
+                loss, gout = self._multimodal_loss(out, gt, mask, den, share)
             else:
                 kind = KINDS[self.variant]
                 grid, half = None, 0.0
@@ -321,13 +419,17 @@ class TrainStep:
                     half = (model.disp_max - model.disp_min) / model.steps / 2.0
                 pad = self.loss_padding
                 if pad is not None and kind == loss_mod.KIND_UPR:     # train/cli.py:221-222: only the UPR loss takes it
-                    mp = (torch.abs(gt) < pad).int()
-                    aux = self._scaled_aux(self._aux_override(loss_mod.KIND_UPR_PADDED, gt, mp))
+                    if share is None:
+                        mp = (torch.abs(gt) < pad).int()
+                        aux = self._scaled_aux(self._aux_override(loss_mod.KIND_UPR_PADDED, gt, mp))
+                    else:
+                        mp, aux = share.mp[share.index], share.chunk_aux(mask.numel())
                     loss, gout = loss_mod.native_multi_loss(loss_mod.KIND_UPR_PADDED, out, gt, mask, mp, None, 0.0,
                                                             True, den, aux)
                 else:
                     loss, gout = loss_mod.native_loss(kind, out, gt, mask, grid, half, True, den)
-            on_done = (lambda key: self.buckets.ready(self.grad, key)) if self.distributed else None
+            hooked = self.distributed and (share is None or share.last())
+            on_done = (lambda key: self.buckets.ready(self.grad, key)) if hooked else None
             model._trunk.backward(p, tape, gout, self._trainable_grads or None, on_done)
         return loss
 
@@ -340,9 +442,11 @@ class TrainStep:
         mpi[:, :, 3] *= (torch.abs(mpi[:, :, 4]) < self.loss_padding).float()
         return mpi
 
-    def _multimodal_heads_loss(self, heads, mpi, mask):
+    def _multimodal_heads_loss(self, heads, mpi, mask, share=None):
         model = self.model
         mpi = self._padded_mpi(mpi)
+        if self.variant == 'upr' and share is not None:
+            return self._whole_batch_upr_loss(loss_mod.KIND_MULTI_UPR, heads, mpi, mask, None, share)
         if self.variant == 'upr':
             return loss_mod.ImprovedMultiUncertaintyL1Loss()(heads, mpi, mask)
         if self.variant == 'dpp':
@@ -355,15 +459,45 @@ class TrainStep:
         reference evaluates the loss on the gathered batch, train/cli.py:245-255)"""
         if not self.distributed:
             return None
+        return self._aux_sums(kind, target[:, :, 3].sum(1) if kind == loss_mod.KIND_MULTI_UPR else None, mask_padding)
+
+    def _aux_sums(self, kind, tot, mask_padding):
+        """the two sums themselves, over this rank's tensors and then over the ranks.  tot: the total alpha per pixel (the
+        multimodal UPR loss: its sum and the count of pixels without a surface); mask_padding: the padded UPR loss's in-range
+        mask (its count)"""
         if kind == loss_mod.KIND_MULTI_UPR:
-            tot = target[:, :, 3].sum(1)
             aux = torch.stack([tot.sum().double(), (tot < 0.01).sum().double()])
         else:
-            aux = torch.stack([mask_padding.sum().double(), torch.zeros((), dtype=torch.float64, device=target.device)])
-        dist.all_reduce(aux, group=self.group)
+            aux = torch.stack([mask_padding.sum().double(), torch.zeros((), dtype=torch.float64, device=mask_padding.device)])
+        if self.distributed:
+            dist.all_reduce(aux, group=self.group)
         return aux
 
-    def _multimodal_loss(self, out, mpi, mask, den):
+    def _whole_batch_upr_loss(self, kind, heads, target, mask, mask_padding, share):
+        """The multimodal UPR / padded UPR loss of a chunk on the stock path, with the whole batch's normalisers where the loss
+        modules form a tensor's own (loss.py:336-372, 264-294): the masked mean over the chunk of
+        ((exp(-logvar) |mean - d_p| + logvar) alpha_p summed over the planes / mean total alpha - logvar * oor * pixels / #oor) / 2,
+        resp. ((exp(-logvar) |mean - gt| + logvar) * in * pixels / #in - logvar * (1 - in) * pixels / #(1 - in)) / 2
+        (a factor whose count is 0 is 1).  On the GPU the fused kernel with its aux_override, as the native path calls it."""
+        mean, logvar = heads['mean'], heads['logvar']
+        if mean.is_cuda:
+            return loss_mod._NativeMultiLossFn.apply(kind, target, mask, mask_padding, share.chunk_aux(mask.numel()),
+                                                     mean, logvar)
+        s0, s1, n = share.aux[0], share.aux[1], float(share.pixels)
+        if kind == loss_mod.KIND_MULTI_UPR:
+            weights, targets = target[:, :, 3], target[:, :, 4]
+            loss = torch.exp(-logvar).unsqueeze(1) * torch.abs(mean.unsqueeze(1) - targets) + logvar.unsqueeze(1)
+            loss = (loss * weights).sum(1) / (s0 / n).float()
+            oor = (weights.sum(1) < 0.01).float()
+            loss_oor = -logvar * oor * (n / s1).float()          # 0 * inf = NaN when no pixel lacks a surface, as in the reference
+        else:
+            mp = mask_padding.float()
+            one = torch.ones_like(s0)
+            loss = (torch.exp(-logvar) * torch.abs(mean - target) + logvar) * mp * torch.where(s0 > 0, n / s0, one).float()
+            loss_oor = -logvar * (1.0 - mp) * torch.where(n - s0 > 0, n / (n - s0), one).float()
+        return loss_mod._masked_mean((loss + loss_oor) / 2.0, mask)
+
+    def _multimodal_loss(self, out, mpi, mask, den, share=None):
         """multimodal losses over (B,P,5,H,W) targets: fused HIP value + gradient (mmlf_loss_multi_fwd_bwd)"""
         model = self.model
         mpi = self._padded_mpi(mpi)
@@ -372,21 +506,31 @@ class TrainStep:
         if kind == loss_mod.KIND_MULTI_CE:
             grid = model._grid('torch', out.device)
             half = (model.disp_max - model.disp_min) / model.steps / 2.0
-        aux = self._aux_override(kind, mpi, None) if kind == loss_mod.KIND_MULTI_UPR else None
-        return loss_mod.native_multi_loss(kind, out, mpi, mask, None, grid, half, True, den, self._scaled_aux(aux))
+        if share is not None:                   # a chunk of a step: the whole batch's sums, scaled to the chunk's pixels
+            aux = share.chunk_aux(mask.numel()) if kind == loss_mod.KIND_MULTI_UPR else None
+        else:
+            aux = self._scaled_aux(self._aux_override(kind, mpi, None) if kind == loss_mod.KIND_MULTI_UPR else None)
+        return loss_mod.native_multi_loss(kind, out, mpi, mask, None, grid, half, True, den, aux)
 
     def _scaled_aux(self, aux):
         # the kernel forms mean = aux[0] / n_local and n_local / aux[1]: pass the global sums divided by the world size
         return None if aux is None else aux / self.world
 
-    def _torch_fwd_bwd(self, h, v, i_, d, gt, mask, den):
+    def _torch_fwd_bwd(self, h, v, i_, d, gt, mask, den, share=None):
+        """share: this pass is a chunk of a step (_Chunks), None: the whole step.  `.grad` accumulates over the chunks and goes
+        to the flat gradient behind the last one."""
         model = self.model
-        for _, p in model.named_parameters():
-            p.grad = None
+        if share is None or share.first():
+            for _, p in model.named_parameters():
+                p.grad = None
         out = model(h, v, i_, d)
         den = self._den_end(den)
+        if share is not None:
+            share.den = den
         if self.multimodal:
-            loss = self._multimodal_heads_loss(out, gt, mask)
+            loss = self._multimodal_heads_loss(out, gt, mask, share)
+        elif self.variant == 'upr' and share is not None and self.loss_padding is not None:
+            loss = self._whole_batch_upr_loss(loss_mod.KIND_UPR_PADDED, out, gt, mask, share.mp[share.index], share)
         elif self.variant == 'upr':
             mp = None if self.loss_padding is None else (torch.abs(gt) < self.loss_padding).int()
             loss = loss_mod.ImprovedUncertaintyL1Loss()(out, gt, mask, mp)
@@ -399,6 +543,8 @@ class TrainStep:
             cnt = mask.sum().double()
             loss = loss * (cnt / den.squeeze()).float() if cnt > 0 else loss
         loss.backward()
+        if share is not None and not share.last():
+            return loss.detach()
         for name, p in model.named_parameters():
             if p.grad is not None:          # (a frozen parameter: its slice of the flat gradient stays zero)
                 self._grads[name].copy_(p.grad)
