@@ -148,6 +148,49 @@ def call(name, *args):
         raise RuntimeError(f'{name} failed: {last_error()}')
 
 
+# ---- libmmlf_eval_hip.so: the multimodal evaluation kernels (include/mmlf_eval_hip.h), an ABI of their own ----
+EVAL_LIB_PATH = os.path.join(_HERE, 'csrc', 'libmmlf_eval_hip.so')
+_EVAL_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'mmlf_eval_hip.h')
+
+
+def _eval_header_text():
+    with open(_EVAL_HEADER) as f:
+        return f.read()
+
+
+EVAL_SIGNATURES = signatures_from_header(_eval_header_text())
+EVAL_ABI_VERSION = int(re.search(r'^#define\s+MMLF_EVAL_ABI_VERSION\s+(\d+)', _eval_header_text(), re.M).group(1))
+_eval_lib = None
+
+
+def load_eval():
+    """Load libmmlf_eval_hip.so once; raise if it is absent or of another ABI version (no fallback).  torch is imported at
+    this module's top, ahead of the library, for the reason load() gives."""
+    global _eval_lib
+    if _eval_lib is None:
+        if not os.path.exists(EVAL_LIB_PATH):
+            raise RuntimeError(f'{EVAL_LIB_PATH} not found: build it with `python -m mmlf_amd.csrc.build` '
+                               '(the multimodal evaluation has no fallback on CUDA tensors)')
+        lib = ctypes.CDLL(EVAL_LIB_PATH)
+        got = lib.mmlf_eval_abi_version() if hasattr(lib, 'mmlf_eval_abi_version') else None
+        if got != EVAL_ABI_VERSION:
+            raise RuntimeError(f'{EVAL_LIB_PATH} implements ABI version {got}, this package needs {EVAL_ABI_VERSION}: '
+                               'rebuild it with `python -m mmlf_amd.csrc.build --force`')
+        for name, (res, args) in EVAL_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _eval_lib = lib
+    return _eval_lib
+
+
+def call_eval(name, *args):
+    """Invoke an int-returning entry point of the evaluation library; nonzero status -> RuntimeError."""
+    lib = load_eval()
+    if getattr(lib, name)(*args) != 0:
+        raise RuntimeError(f'{name} failed: {lib.mmlf_eval_last_error().decode()}')
+
+
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

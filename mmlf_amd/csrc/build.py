@@ -72,6 +72,33 @@ def build(force=False, verbose=True, extra_flags=(), lib=None):
     return lib
 
 
+# The multimodal evaluation (include/mmlf_eval_hip.h) is a library of its own: none of its files is in SOURCES or HASHED, so
+# neither libmmlf_hip.so nor its `src=` hash changes when an evaluation kernel does.
+EVAL_SOURCES = ['evaluate.hip']
+EVAL_LIB = os.path.join(HERE, 'libmmlf_eval_hip.so')
+EVAL_HEADER = os.path.join(HERE, '..', '..', 'include', 'mmlf_eval_hip.h')
+
+
+def eval_stale():
+    if not os.path.exists(EVAL_LIB):
+        return True
+    t = os.path.getmtime(EVAL_LIB)
+    deps = [os.path.join(HERE, s) for s in EVAL_SOURCES] + [os.path.join(HERE, 'build.py'), EVAL_HEADER]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_eval(force=False, verbose=True):
+    """libmmlf_eval_hip.so, with the FLAGS of the training library (-ffp-contract=off: its float64 arithmetic is written
+    operation by operation)"""
+    if not force and not eval_stale():
+        return EVAL_LIB
+    cmd = [HIPCC, *FLAGS, '-shared', *[os.path.join(HERE, s) for s in EVAL_SOURCES], '-o', EVAL_LIB]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return EVAL_LIB
+
+
 if __name__ == '__main__':
     if '--source-hash' in sys.argv:
         print(source_hash())
@@ -79,3 +106,4 @@ if __name__ == '__main__':
         print(source_revision())
     else:
         build(force='--force' in sys.argv)
+        build_eval(force='--force' in sys.argv)

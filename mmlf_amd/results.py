@@ -112,3 +112,17 @@ def save_batch(path, scene_names, index, gt=None, result=None, uncert=None, runt
         if runtime is not None:
             with open(os.path.join(runtimes, f'{scene}.txt'), 'w') as f:
                 f.write(str(runtime / float(idx.shape[0])))
+
+
+def save_multimodal(path, scene_names, index, gt_modes, mode_prop):
+    """Beside save_batch's files: <path>/scenes/<scene>/gt_modes.npy, the (h, w, 2) float64 ground-truth modes as reference
+    validate/cluster.py:64 saves them (image orientation, not flipped), and mode_prop.pfm, the float32 mode proportion
+    vertically flipped as utils/modecnt.py:82-83 writes it.  gt_modes: (b, h, w, 2); mode_prop: (b, h, w)."""
+    gt_modes, mode_prop = _np(gt_modes), _np(mode_prop)
+    idx = _np(index)
+    idx = idx.squeeze(1) if idx.ndim == 2 else idx.reshape(-1)
+    for arr_i, i in enumerate(idx.tolist()):
+        scene_dir = os.path.join(path, 'scenes', scene_names[int(i)])
+        os.makedirs(scene_dir, exist_ok=True)
+        np.save(os.path.join(scene_dir, 'gt_modes.npy'), gt_modes[arr_i])
+        pfm.save(os.path.join(scene_dir, 'mode_prop.pfm'), np.flip(mode_prop[arr_i].astype(np.float32), 0))

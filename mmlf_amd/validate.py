@@ -47,7 +47,7 @@ def table_rows(avg, runtime):
 
 @torch.no_grad()
 def validate_scenes(model, scenes, val_disp_min=-3.5, val_disp_max=3.5, margin=15, out_dir=None, scene_names=None,
-                    n_bins=108, reference_compat=True):
+                    n_bins=108, reference_compat=True, multimodal=False):
     """The validation loop of reference mmlf/validate/cli.py:249-351 on device tensors: per scene the forward pass
     (FeedForward or Ensamble), masked MSE / BadPix(0.07) with a `margin`-px frame removed, the predictive distribution on
     `n_bins` disparity bins (Ensamble: Laplace mixture of its members; DPP: the posterior; UPR: one Laplace; BASE: the bin
@@ -65,7 +65,16 @@ def validate_scenes(model, scenes, val_disp_min=-3.5, val_disp_max=3.5, margin=1
     as the reference's do (it saves before it evaluates).  reference_compat=False evaluates every metric on distributions
     smoothed exactly once (what the helper functions compute when called on fresh arrays).
     `runtime` stops where the reference's clock does (validate/cli.py:309): after the forward pass and the host copies,
-    before any distribution metric."""
+    before any distribution metric.
+
+    multimodal=True adds the headline evaluation of the paper, which the reference runs as post-hoc scripts over the saved
+    files (multimodal.py of this package): per row the sums `mm_cnt`, `mm_mse_sum`, `mm_badpix_sum`, `um_mse_sum`,
+    `um_badpix_sum`, `mm_few_modes` of `multimodal.two_mode_error` on the model's `posterior` (the Ensamble's mixture, DPP's
+    softmax, UPR's Laplace) and `mode_cnt_share`, the share of pixels whose smoothed posterior keeps two maxima; in the
+    averages `mm_mse`, `mm_badpix`, `um_mse`, `um_badpix` as TOTAL sums over the TOTAL count across scenes
+    (validate/multimodal.py:93-94), not a mean of per-scene means; with out_dir also `gt_modes.npy` and `mode_prop.pfm` per
+    scene.  A model without a posterior (BASE) gets none of these keys.  With the default False nothing is computed,
+    launched or written beyond the above."""
     import time
     from . import dl, metrics, results
     if out_dir is not None and scene_names is None:
@@ -111,6 +120,22 @@ def validate_scenes(model, scenes, val_disp_min=-3.5, val_disp_max=3.5, margin=1
         row['kld_um'] = float(metrics.kl_divergence(dist, dist_gt, 1.0 - mm, inplace=seq))
         row['nll'] = float(nll)
         row['runtime'] = runtime
+        if multimodal and output.get('posterior') is not None:
+            from . import multimodal as mm_mod
+            owner = model if hasattr(model, 'disp_min') else inner           # the bins' range is the model's own
+            gt32 = gt.float().contiguous()
+            modes_gt = mm_mod.gt_modes(gt32)
+            n_modes, mode_disp, mode_cnt, mode_prop = mm_mod.posterior_analysis(
+                output['posterior'].contiguous(), owner.disp_min, owner.disp_max)
+            sums = mm_mod.two_mode_error(mode_disp, n_modes, modes_gt, gt32, mean.float().contiguous(), margin)
+            row.update(zip(mm_mod.TWO_MODE_FIELDS, sums.tolist()))
+            row['mode_cnt_share'] = float(mode_cnt.double().mean())
+            if out_dir is not None:
+                results.save_multimodal(out_dir, scene_names, index, modes_gt, mode_prop)
         rows.append(row)
     avg = {k: sum(r[k] for r in rows) / max(1, len(rows)) for k in ('mse', 'badpix', 'kld', 'kld_mm', 'kld_um', 'nll')}
+    if multimodal and rows and all('mm_cnt' in r for r in rows):
+        cnt = sum(r['mm_cnt'] for r in rows)
+        for k in ('mm_mse', 'mm_badpix', 'um_mse', 'um_badpix'):
+            avg[k] = sum(r[k + '_sum'] for r in rows) / cnt if cnt else float('nan')
     return rows, avg
