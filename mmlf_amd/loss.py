@@ -3,8 +3,12 @@
 Each module takes ``(output_dict, target, mask[, mask_padding])`` like the reference.  On CUDA
 tensors the training losses -- single-mode, multimodal and padded -- run fused HIP kernels (value +
 gradient in one call, ``mmlf_loss_fwd_bwd`` / ``mmlf_loss_multi_fwd_bwd``) behind a small autograd node;
-on CPU they are plain torch expressions.
+on CPU they are plain torch expressions.  ``LOSSES`` lists the seven kinds: what ``native_loss`` and the
+node know about a kind is its row.
 """
+import functools
+from typing import NamedTuple
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -13,7 +17,7 @@ from . import _lib
 from ._lib import call, check, ptr
 from .engine import LOSS_BLOCKS
 
-KIND_L1, KIND_UPR, KIND_CE = 0, 1, 2
+KIND_L1, KIND_UPR, KIND_CE = 0, 1, 2                                         # mmlf_loss_fwd_bwd
 KIND_MULTI_L1, KIND_MULTI_UPR, KIND_MULTI_CE, KIND_UPR_PADDED = 3, 4, 5, 6   # mmlf_loss_multi_fwd_bwd
 
 
@@ -29,115 +33,6 @@ def create_mask_margin(shape, margin=0):
     return mask
 
 
-def _check_loss_args(dev, n, oc, mask, grid_torch, den_override):
-    """what both fused losses take: the kernels walk n = B*H*W mask pixels (converted by the caller: any dtype, any strides),
-    oc grid entries and one float64 denominator -- a shorter tensor, or one of another device, is read past its end"""
-    check(mask, 'loss: mask', dev, None, numel=n, contiguous=False)
-    if grid_torch is not None:
-        check(grid_torch, 'loss: grid', dev, min_numel=oc)
-    if den_override is not None:
-        check(den_override, 'loss: den_override', dev, torch.float64, min_numel=1)
-
-
-def native_loss(kind, output, gt, mask, grid_torch=None, half_step=0.0, want_grad=True, den_override=None):
-    """Fused loss on the raw trunk output (B,oc,H,W).  Returns (loss scalar tensor, grad or None)."""
-    B, oc, H, W = output.shape
-    dev = output.device
-    _check_loss_args(dev, B * H * W, oc, mask, grid_torch, den_override)
-    check(gt, 'loss: target', dev, None, numel=B * H * W, contiguous=False)
-    output = output.contiguous()
-    gt = gt.contiguous().float()
-    mask = mask.contiguous().to(torch.int32)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    grad = torch.empty_like(output) if want_grad else None
-    if want_grad and kind != KIND_CE and oc > (1 if kind == KIND_L1 else 2):
-        grad.zero_()
-    scratch = torch.empty(2 * LOSS_BLOCKS + 2, dtype=torch.float64, device=dev)
-    call('mmlf_loss_fwd_bwd', kind, ptr(output), oc, ptr(gt), ptr(mask), ptr(grid_torch), float(half_step),
-         ptr(loss), ptr(grad), ptr(scratch), LOSS_BLOCKS, ptr(den_override), B, H, W, _lib.stream_ptr())
-    return loss, grad
-
-
-def native_multi_loss(kind, output, target, mask, mask_padding=None, grid_torch=None, half_step=0.0, want_grad=True,
-                      den_override=None, aux_override=None):
-    """Fused multimodal / padded loss on the raw trunk output (B,oc,H,W); target = mpi (B,P,5,H,W), or gt (B,H,W)
-    for KIND_UPR_PADDED.  Returns (loss scalar tensor, grad or None)."""
-    B, oc, H, W = output.shape
-    dev = output.device
-    _check_loss_args(dev, B * H * W, oc, mask, grid_torch, den_override)
-    check(target, 'loss: target', dev, None, contiguous=False)        # (its shape: below, by kind)
-    if mask_padding is not None:
-        check(mask_padding, 'loss: mask_padding', dev, None, numel=B * H * W, contiguous=False)
-    if aux_override is not None:
-        check(aux_override, 'loss: aux_override', dev, torch.float64, min_numel=2)
-    output = output.contiguous()
-    target = target.contiguous().float()
-    P = 0
-    if kind != KIND_UPR_PADDED:
-        if target.dim() != 5 or target.shape[0] != B or target.shape[2] != 5 or tuple(target.shape[3:]) != (H, W):
-            raise ValueError(f'multimodal loss: target must be (B, P, 5, H, W), got {tuple(target.shape)}')
-        P = target.shape[1]
-    elif tuple(target.shape) != (B, H, W) or mask_padding is None:
-        raise ValueError('padded loss: target (B, H, W) and mask_padding required')
-    mask = mask.contiguous().to(torch.int32)
-    if mask_padding is not None:
-        mask_padding = mask_padding.contiguous().to(torch.int32)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    grad = None
-    if want_grad:
-        full = kind == KIND_MULTI_CE or oc == (1 if kind == KIND_MULTI_L1 else 2)
-        grad = torch.empty_like(output) if full else torch.zeros_like(output)
-    n = int(_lib.load().mmlf_loss_multi_scratch_doubles(LOSS_BLOCKS))
-    scratch = torch.empty(n, dtype=torch.float64, device=dev)
-    call('mmlf_loss_multi_fwd_bwd', kind, ptr(output), oc, ptr(target), P, ptr(mask), ptr(mask_padding),
-         ptr(grid_torch), float(half_step), ptr(loss), ptr(grad), ptr(scratch), LOSS_BLOCKS, ptr(den_override),
-         ptr(aux_override), B, H, W, _lib.stream_ptr())
-    return loss, grad
-
-
-class _NativeMultiLossFn(torch.autograd.Function):
-    """autograd node of the multimodal / padded losses for callers that go through the loss modules.  aux: the kernel's
-    aux_override (a micro-batch of a train step hands in the whole batch's sums), None: the tensor's own sums"""
-
-    @staticmethod
-    def forward(ctx, kind, target, mask, mask_padding, aux, *heads):
-        out = torch.stack(list(heads), 1)
-        loss, grad = native_multi_loss(kind, out.detach(), target, mask, mask_padding, aux_override=aux)
-        ctx.save_for_backward(grad)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        (grad,) = ctx.saved_tensors
-        g = grad * gl
-        return (None, None, None, None, None) + tuple(g[:, k] for k in range(g.shape[1]))
-
-
-class _NativeLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, kind, gt, mask, grid, half_step, *heads):
-        # heads: (mean,) | (mean, logvar) | (scores,)
-        out = heads[0].unsqueeze(1) if kind != KIND_CE else heads[0]
-        if kind == KIND_UPR:
-            out = torch.stack([heads[0], heads[1]], 1)
-        loss, grad = native_loss(kind, out.detach(), gt, mask, grid, half_step, True)
-        ctx.kind = kind
-        ctx.save_for_backward(grad)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        (grad,) = ctx.saved_tensors
-        g = grad * gl
-        if ctx.kind == KIND_L1:
-            hg = (g[:, 0],)
-        elif ctx.kind == KIND_UPR:
-            hg = (g[:, 0], g[:, 1])
-        else:
-            hg = (g,)
-        return (None, None, None, None, None) + hg
-
-
 def _masked_mean(loss, mask):
     count = mask.int().sum()
     loss = loss * mask.float()
@@ -146,12 +41,16 @@ def _masked_mean(loss, mask):
     return loss.sum() / count
 
 
+def _fused(kind, target, mask, mask_padding, *heads):
+    return _NativeLossFn.apply(kind, target, mask, mask_padding, None, 0.0, None, *heads)
+
+
 class MaskedL1Loss(nn.Module):
     """loss.py:29-77"""
 
     def forward(self, input, target, mask):
         if input['mean'].is_cuda:
-            return _NativeLossFn.apply(KIND_L1, target, mask, None, 0.0, input['mean'])
+            return _fused(KIND_L1, target, mask, None, input['mean'])
         return _masked_mean(torch.abs(input['mean'] - target), mask)
 
 
@@ -182,10 +81,8 @@ class ImprovedUncertaintyL1Loss(nn.Module):
 
     def forward(self, input, target, mask, mask_padding=None):
         mean, logvar = input['mean'], input['logvar']
-        if mean.is_cuda and mask_padding is None:
-            return _NativeLossFn.apply(KIND_UPR, target, mask, None, 0.0, mean, logvar)
-        if mean.is_cuda:
-            return _NativeMultiLossFn.apply(KIND_UPR_PADDED, target, mask, mask_padding, None, mean, logvar)
+        if mean.is_cuda:        # without a mask_padding this is kind 1, not kind 6 with a mask of ones
+            return _fused(KIND_UPR if mask_padding is None else KIND_UPR_PADDED, target, mask, mask_padding, mean, logvar)
         loss = torch.exp(-logvar) * torch.abs(mean - target) + logvar
         if mask_padding is not None:
             mp = mask_padding.float()
@@ -217,7 +114,7 @@ class MultiMaskedL1Loss(nn.Module):
 
     def forward(self, input, target, mask):
         if input['mean'].is_cuda:
-            return _NativeMultiLossFn.apply(KIND_MULTI_L1, target, mask, None, None, input['mean'])
+            return _fused(KIND_MULTI_L1, target, mask, None, input['mean'])
         weights, targets = target[:, :, 3], target[:, :, 4]
         diff = (torch.abs(input['mean'].unsqueeze(1) - targets) * weights).sum(1)
         return _masked_mean(diff, mask)
@@ -230,7 +127,7 @@ class ImprovedMultiUncertaintyL1Loss(nn.Module):
     def forward(self, input, target, mask, mask_padding=None):
         mean, logvar = input['mean'], input['logvar']
         if mean.is_cuda:
-            return _NativeMultiLossFn.apply(KIND_MULTI_UPR, target, mask, None, None, mean, logvar)
+            return _fused(KIND_MULTI_UPR, target, mask, None, mean, logvar)
         weights, targets = target[:, :, 3], target[:, :, 4]
         loss = torch.exp(-logvar).unsqueeze(1) * torch.abs(mean.unsqueeze(1) - targets) + logvar.unsqueeze(1)
         total = weights.sum(1)
@@ -238,3 +135,100 @@ class ImprovedMultiUncertaintyL1Loss(nn.Module):
         oor = (total < 0.01).float()
         loss_oor = -logvar * oor * (oor.numel() / torch.sum(oor))
         return _masked_mean((loss + loss_oor) / 2.0, mask)
+
+
+# ------------------------------------------------------------------ the seven fused kinds
+class LossKind(NamedTuple):
+    entry: str              # the C entry point
+    heads: tuple            # the heads it consumes, in the channel order of the trunk output
+    written: int            # gradient channels the kernel writes (0: all of them); the rest must be zeroed
+    target: str             # 'gt': (B, H, W) depths, 'mpi': (B, P, 5, H, W) planes
+    mask_padding: bool      # takes the in-range mask
+    grid: bool              # takes the disparity grid and half a step of it (the cross-entropy target is built in the kernel)
+    aux: bool               # normalises by whole-batch sums (aux_override; NULL: the tensor's own)
+    module: type            # the nn.Module that states it on CPU (the cross-entropy kinds: on reg_to_class / mpi_to_weights targets)
+
+
+_SINGLE, _MULTI = 'mmlf_loss_fwd_bwd', 'mmlf_loss_multi_fwd_bwd'
+LOSSES = {
+    KIND_L1:         LossKind(_SINGLE, ('mean',), 1, 'gt', False, False, False, MaskedL1Loss),
+    KIND_UPR:        LossKind(_SINGLE, ('mean', 'logvar'), 2, 'gt', False, False, False, ImprovedUncertaintyL1Loss),
+    KIND_CE:         LossKind(_SINGLE, ('scores',), 0, 'gt', False, True, False, MaskedCrossEntropy),
+    KIND_MULTI_L1:   LossKind(_MULTI, ('mean',), 1, 'mpi', False, False, False, MultiMaskedL1Loss),
+    KIND_MULTI_UPR:  LossKind(_MULTI, ('mean', 'logvar'), 2, 'mpi', False, False, True, ImprovedMultiUncertaintyL1Loss),
+    KIND_MULTI_CE:   LossKind(_MULTI, ('scores',), 0, 'mpi', False, True, False, MaskedCrossEntropy),
+    KIND_UPR_PADDED: LossKind(_MULTI, ('mean', 'logvar'), 2, 'gt', True, False, True, ImprovedUncertaintyL1Loss),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _scratch_doubles(entry):
+    return 2 * LOSS_BLOCKS + 2 if entry == _SINGLE else int(_lib.load().mmlf_loss_multi_scratch_doubles(LOSS_BLOCKS))
+
+
+def native_loss(kind, output, target, mask, mask_padding=None, grid_torch=None, half_step=0.0, want_grad=True,
+                den_override=None, aux_override=None):
+    """Fused loss of LOSSES[kind] on the raw trunk output (B,oc,H,W).  The kernels walk n = B*H*W pixels of mask, mask_padding
+    and a gt target (any dtype, any strides: converted here), oc grid entries, one float64 denominator and two float64 sums --
+    a shorter tensor, or one of another device, is read past its end.  Returns (loss scalar tensor, grad or None)."""
+    row = LOSSES[kind]
+    B, oc, H, W = output.shape
+    dev, n = output.device, B * H * W
+    check(mask, 'loss: mask', dev, None, numel=n, contiguous=False)
+    if grid_torch is not None:
+        check(grid_torch, 'loss: grid', dev, min_numel=oc)
+    if den_override is not None:
+        check(den_override, 'loss: den_override', dev, torch.float64, min_numel=1)
+    check(target, 'loss: target', dev, None, numel=n if row.target == 'gt' else None, contiguous=False)
+    if mask_padding is not None:
+        check(mask_padding, 'loss: mask_padding', dev, None, numel=n, contiguous=False)
+    if aux_override is not None:
+        check(aux_override, 'loss: aux_override', dev, torch.float64, min_numel=2)
+    if row.target == 'mpi' and (target.dim() != 5 or target.shape[0] != B or target.shape[2] != 5
+                                or tuple(target.shape[3:]) != (H, W)):
+        raise ValueError(f'multimodal loss: target must be (B, P, 5, H, W), got {tuple(target.shape)}')
+    if row.mask_padding and (tuple(target.shape) != (B, H, W) or mask_padding is None):
+        raise ValueError('padded loss: target (B, H, W) and mask_padding required')
+    output = output.contiguous()
+    target = target.contiguous().float()
+    mask = mask.contiguous().to(torch.int32)
+    if mask_padding is not None:
+        mask_padding = mask_padding.contiguous().to(torch.int32)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    grad = None
+    if want_grad:
+        grad = torch.zeros_like(output) if 0 < row.written < oc else torch.empty_like(output)
+    scratch = torch.empty(_scratch_doubles(row.entry), dtype=torch.float64, device=dev)
+    if row.entry == _SINGLE:
+        call(_SINGLE, kind, ptr(output), oc, ptr(target), ptr(mask), ptr(grid_torch), float(half_step), ptr(loss), ptr(grad),
+             ptr(scratch), LOSS_BLOCKS, ptr(den_override), B, H, W, _lib.stream_ptr())
+    else:
+        call(_MULTI, kind, ptr(output), oc, ptr(target), target.shape[1] if row.target == 'mpi' else 0, ptr(mask),
+             ptr(mask_padding), ptr(grid_torch), float(half_step), ptr(loss), ptr(grad), ptr(scratch), LOSS_BLOCKS,
+             ptr(den_override), ptr(aux_override), B, H, W, _lib.stream_ptr())
+    return loss, grad
+
+
+native_multi_loss = native_loss
+
+
+class _NativeLossFn(torch.autograd.Function):
+    """autograd node of the fused losses for callers that go through the loss modules.  heads: LOSSES[kind].heads; aux: the
+    kernel's aux_override (a micro-batch of a train step hands in the whole batch's sums), None: the tensor's own sums"""
+
+    @staticmethod
+    def forward(ctx, kind, target, mask, mask_padding, grid, half_step, aux, *heads):
+        if LOSSES[kind].heads == ('scores',):
+            out = heads[0]
+        else:
+            out = heads[0].unsqueeze(1) if len(heads) == 1 else torch.stack(heads, 1)
+        loss, grad = native_loss(kind, out.detach(), target, mask, mask_padding, grid, half_step, aux_override=aux)
+        ctx.stacked = out is not heads[0]
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        (grad,) = ctx.saved_tensors
+        g = grad * gl
+        return (None,) * 7 + (tuple(g[:, k] for k in range(g.shape[1])) if ctx.stacked else (g,))

@@ -25,8 +25,6 @@ import torch.distributed as dist
 from . import _lib, dl, loss as loss_mod
 from ._lib import call, ptr
 
-KINDS = {'base': loss_mod.KIND_L1, 'upr': loss_mod.KIND_UPR, 'dpp': loss_mod.KIND_CE}
-
 
 def flatten_parameters(model):
     """Re-point every parameter at a view of ONE flat float32 buffer (state_dict keys, shapes and
@@ -68,8 +66,7 @@ def validation_pass(val_model, batches, uncert=False, loss_multimodal=False, mar
     if out_dir is not None and scene_names is None:
         raise ValueError('validation_pass: out_dir needs scene_names (the dataset\'s scenes_names, indexed by `index`)')
     val_model.eval()
-    loss_fn = loss_mod.MultiMaskedL1Loss() if loss_multimodal else loss_mod.MaskedL1Loss()
-    loss_uncert_fn = loss_mod.ImprovedMultiUncertaintyL1Loss() if loss_multimodal else loss_mod.ImprovedUncertaintyL1Loss()
+    loss_fn, loss_uncert_fn = (loss_mod.LOSSES[StepLoss.kind_of(v, loss_multimodal)].module() for v in ('base', 'upr'))
     mse_fn, bad_pix_fn = loss_mod.MaskedMSELoss(), loss_mod.MaskedBadPix()
     loss_val_avg, mse_avg, bad_pix_avg, n = 0.0, 0.0, 0.0, 0
     for data in batches:
@@ -181,16 +178,17 @@ class GradBuckets:
 
 
 class _Chunks:
-    """What the micro-batches of one step share (TrainStep._chunked_fwd_bwd).  index / count: the chunk that runs now; den:
-    the whole batch's loss denominator (under data parallelism first the pending all-reduce that chunk 0 waits for behind its
-    forward pass); aux: the whole batch's sums the multimodal UPR / padded UPR losses normalise by (over all ranks), None for
-    the other losses; pixels: B * H * W of the whole batch, over all ranks; mp: the padded UPR loss's in-range masks, one per
-    chunk; packs: the step's packed filters, made by chunk 0's forward pass (the weights do not change inside a step)."""
-    __slots__ = ('index', 'count', 'den', 'aux', 'pixels', 'mp', 'packs', '_scaled')
+    """What the micro-batches of one step share (made by StepLoss.chunks, ahead of chunk 0).  index / count: the chunk that
+    runs now; den: the whole batch's loss denominator (under data parallelism first the pending all-reduce that chunk 0 waits
+    for behind its forward pass); aux: the whole batch's sums the multimodal UPR / padded UPR losses normalise by (over all
+    ranks), None for the other losses; pixels: B * H * W of the whole batch, over all ranks; mp: the padded UPR loss's in-range
+    masks, one per chunk; scaled: StepLoss.kernel_aux's values per chunk size (at most two occur in a step); packs: the step's
+    packed filters, made by chunk 0's forward pass (the weights do not change inside a step)."""
+    __slots__ = ('index', 'count', 'den', 'aux', 'pixels', 'mp', 'packs', 'scaled')
 
     def __init__(self, count, den, aux, pixels, mp):
         self.index, self.count, self.den, self.aux, self.pixels, self.mp = 0, count, den, aux, pixels, mp
-        self.packs, self._scaled = None, {}
+        self.packs, self.scaled = None, {}
 
     def first(self):
         return self.index == 0
@@ -198,15 +196,151 @@ class _Chunks:
     def last(self):
         return self.index == self.count - 1
 
-    def chunk_aux(self, n):
-        """the whole-batch sums scaled by a chunk's share n / pixels of the pixels: the loss kernel forms aux[0] / n and
-        n / aux[1] from its own n (TrainStep._scaled_aux does the same per rank).  Product first: a sum that equals `pixels`
-        (every pixel in range) comes out as n exactly.  At most two chunk sizes occur in a step."""
-        if self.aux is None:
+
+class StepLoss:
+    """Which loss a train step takes, on which target, divided by what (reference train/cli.py:190-225,247-255).  The kind is
+    a row of loss.LOSSES, fixed at construction; native() evaluates it with the fused kernel on the raw trunk output, torch()
+    with the row's module on the heads.
+
+    A pass is the whole step of one rank, the step of a rank of a process group (the reference evaluates the loss on the
+    gathered batch: every count and sum is the global one), or a chunk of either (share: the step's _Chunks).  What a pass
+    divides by -- `den`, the count of valid pixels, and for the kinds with whole-batch sums (4: sum of total alpha, count of
+    pixels without a surface; 6: count of in-range pixels) `aux` -- with S the all-reduced sums, n the pass's pixels and
+    `pixels` the whole batch's over all ranks:
+
+    | path   | regime          | den                                   | aux                                                 |
+    |--------|-----------------|---------------------------------------|-----------------------------------------------------|
+    | native | one rank        | None: the kernel counts its mask      | None: the kernel forms its own sums                 |
+    | native | rank of a group | all-reduced count / world             | S / world                                           |
+    | native | chunk           | the whole batch's count (/ world)     | S * n / pixels                                      |
+    | torch  | one rank        | None: the module's own masked mean    | the module's own sums                               |
+    | torch  | rank of a group | loss * own count / (count / world)    | the module's own sums: the RANK's, not the batch's  |
+    | torch  | chunk           | loss * own count / the batch's count  | S and pixels in the module's expression (on CUDA    |
+    |        |                 |                                       | tensors the kernel with S * n / pixels)             |
+
+    The kernel forms aux[0] / n and n / aux[1] from its own n, hence the scaled sums.  `den` comes from TrainStep._den_begin /
+    _den_end and from chunks()."""
+
+    @staticmethod
+    def kind_of(variant, multimodal, padding=None):
+        """train/cli.py:120-128,247-255; mask_padding reaches the UPR loss alone (:221-222,248): kind 6, and without one the
+        UPR loss stays kind 1"""
+        kind = {'base': (loss_mod.KIND_L1, loss_mod.KIND_MULTI_L1), 'upr': (loss_mod.KIND_UPR, loss_mod.KIND_MULTI_UPR),
+                'dpp': (loss_mod.KIND_CE, loss_mod.KIND_MULTI_CE)}[variant][bool(multimodal)]
+        return loss_mod.KIND_UPR_PADDED if kind == loss_mod.KIND_UPR and padding is not None else kind
+
+    def __init__(self, variant, multimodal, padding, strongest, model, distributed=False, group=None, world=1):
+        self.kind = self.kind_of(variant, multimodal, padding)
+        self.row = row = loss_mod.LOSSES[self.kind]
+        self.module = row.module()
+        self.model, self.padding, self.strongest = model, padding, bool(strongest)
+        # --train_loss_padding with --train_loss_multimodal: planes outside the range lose their alpha (train/cli.py:219-220).
+        # The DPP target is built from the UNPADDED planes (:201-204 run before :219)
+        self.pads_planes = row.target == 'mpi' and padding is not None and not row.grid
+        self.half_step = (model.disp_max - model.disp_min) / model.steps / 2.0 if row.grid else 0.0
+        self.distributed, self.group, self.world = distributed, group, world
+
+    # ------------------------------------------------------------------ the target
+    def step_target(self, gt):
+        """--train_loss_strongest (train/cli.py:190-192): `gt` is the multi-plane tensor, the target its strongest depth"""
+        return TrainStep.strongest_gt(gt).contiguous() if self.strongest else gt
+
+    def _alpha(self, mpi):
+        alpha = mpi[:, :, 3]
+        return alpha * (torch.abs(mpi[:, :, 4]) < self.padding).float() if self.pads_planes else alpha
+
+    def _pass_target(self, target, share):
+        """(target, mask_padding) of a pass; mask_padding = |gt| < padding for kind 6 only (train/cli.py:221-222)"""
+        if self.pads_planes:
+            target = target.clone()
+            target[:, :, 3] = self._alpha(target)
+        if not self.row.mask_padding:
+            return target, None
+        return target, (torch.abs(target) < self.padding).int() if share is None else share.mp[share.index]
+
+    # ------------------------------------------------------------------ the normalisers
+    def _sums(self, x):
+        """S of the table: over this rank's tensor, then over the ranks.  x: the in-range mask (kind 6) or the total alpha per
+        pixel (kind 4)"""
+        if self.row.mask_padding:
+            aux = torch.stack([x.sum().double(), torch.zeros((), dtype=torch.float64, device=x.device)])
+        else:
+            aux = torch.stack([x.sum().double(), (x < 0.01).sum().double()])
+        if self.distributed:
+            dist.all_reduce(aux, group=self.group)
+        return aux
+
+    def chunks(self, count, micro_batches, gt, mask, den):
+        """the chunk regime's normalisers, all formed once ahead of chunk 0.  gt, mask: the whole batch's"""
+        if den is None:
+            den = mask.sum().double().reshape(1)
+        aux = mp = None
+        if self.row.mask_padding:
+            whole = (torch.abs(gt) < self.padding).int()
+            aux, mp = self._sums(whole), whole.chunk(micro_batches)
+        elif self.row.aux:
+            aux = self._sums(self._alpha(gt).sum(1))    # (the padded planes' alpha, without a copy of the other planes)
+        return _Chunks(count, den, aux, mask.numel() * self.world, mp)
+
+    def kernel_aux(self, target, mask_padding, n, share=None):
+        """the kernel's aux_override of a pass of n pixels on its (target, mask_padding): the table's native rows"""
+        if not self.row.aux:
             return None
-        if n not in self._scaled:
-            self._scaled[n] = self.aux * n / self.pixels
-        return self._scaled[n]
+        if share is not None:       # product first: a sum that equals `pixels` (every pixel in range) comes out as n exactly
+            if n not in share.scaled:
+                share.scaled[n] = share.aux * n / share.pixels
+            return share.scaled[n]
+        if not self.distributed:
+            return None
+        return self._sums(mask_padding if self.row.mask_padding else target[:, :, 3].sum(1)) / self.world
+
+    # ------------------------------------------------------------------ the two evaluators
+    def native(self, out, target, mask, den, share=None):
+        """fused HIP value + gradient on the raw trunk output: (loss, gout)"""
+        target, mp = self._pass_target(target, share)
+        grid = self.model._grid('torch', out.device) if self.row.grid else None
+        return loss_mod.native_loss(self.kind, out, target, mask, mp, grid, self.half_step, True, den,
+                                    self.kernel_aux(target, mp, mask.numel(), share))
+
+    def torch(self, heads, target, mask, den, share=None):
+        """the row's module on the heads (the cross-entropy kinds: on the class targets of train/cli.py:201-206): loss"""
+        model = self.model
+        target, mp = self._pass_target(target, share)
+        if self.row.aux and share is not None:
+            loss = self._whole_batch_upr(heads, target, mask, mp, share)
+        elif self.row.grid:
+            to_classes = dl.mpi_to_weights if self.row.target == 'mpi' else dl.reg_to_class
+            loss = self.module(heads, to_classes(target, model.disp_min, model.disp_max, model.steps), mask)
+        else:
+            loss = self.module(heads, target, mask, mp) if self.row.mask_padding else self.module(heads, target, mask)
+        if den is not None:     # global masked mean: rescale the local mean to the shared denominator
+            cnt = mask.sum().double()
+            loss = loss * (cnt / den.squeeze()).float() if cnt > 0 else loss
+        return loss
+
+    def _whole_batch_upr(self, heads, target, mask, mask_padding, share):
+        """The multimodal UPR / padded UPR loss of a chunk on the stock path, with the whole batch's normalisers where the loss
+        modules form a tensor's own (loss.py:336-372, 264-294): the masked mean over the chunk of
+        ((exp(-logvar) |mean - d_p| + logvar) alpha_p summed over the planes / mean total alpha - logvar * oor * pixels / #oor) / 2,
+        resp. ((exp(-logvar) |mean - gt| + logvar) * in * pixels / #in - logvar * (1 - in) * pixels / #(1 - in)) / 2
+        (a factor whose count is 0 is 1).  On the GPU the fused kernel with its aux_override, as the native path calls it."""
+        mean, logvar = heads['mean'], heads['logvar']
+        if mean.is_cuda:
+            return loss_mod._NativeLossFn.apply(self.kind, target, mask, mask_padding, None, 0.0,
+                                                self.kernel_aux(target, mask_padding, mask.numel(), share), mean, logvar)
+        s0, s1, n = share.aux[0], share.aux[1], float(share.pixels)
+        if not self.row.mask_padding:
+            weights, targets = target[:, :, 3], target[:, :, 4]
+            loss = torch.exp(-logvar).unsqueeze(1) * torch.abs(mean.unsqueeze(1) - targets) + logvar.unsqueeze(1)
+            loss = (loss * weights).sum(1) / (s0 / n).float()
+            oor = (weights.sum(1) < 0.01).float()
+            loss_oor = -logvar * oor * (n / s1).float()          # 0 * inf = NaN when no pixel lacks a surface, as in the reference
+        else:
+            mp = mask_padding.float()
+            one = torch.ones_like(s0)
+            loss = (torch.exp(-logvar) * torch.abs(mean - target) + logvar) * mp * torch.where(s0 > 0, n / s0, one).float()
+            loss_oor = -logvar * (1.0 - mp) * torch.where(n - s0 > 0, n / (n - s0), one).float()
+        return loss_mod._masked_mean((loss + loss_oor) / 2.0, mask)
 
 
 class TrainStep:
@@ -230,12 +364,9 @@ class TrainStep:
         self.lr, self.warm_start, self.cooling = float(lr), bool(warm_start), int(cooling)
         self.betas, self.eps, self.margin = betas, float(eps), int(loss_margin)
         self.variant = variant or ('upr' if model.uncert else ('dpp' if model.discrete else 'base'))
-        # --train_loss_multimodal: `gt` is the multi-plane tensor (B,P,5,H,W) (train/cli.py:120-123,201-225)
-        self.multimodal, self.loss_padding = bool(loss_multimodal), loss_padding
-        # --train_loss_strongest (train/cli.py:190-192): `gt` is the multi-plane tensor too, and the target is the depth of
-        # the plane with the largest alpha; the CLI rejects it together with --train_loss_multimodal (train/cli.py:61)
-        self.strongest = bool(loss_strongest)
-        assert not (self.strongest and self.multimodal)
+        # --train_loss_multimodal: `gt` is the multi-plane tensor (B,P,5,H,W) (train/cli.py:120-123,201-225); under
+        # --train_loss_strongest too; the CLI rejects the two together (train/cli.py:61)
+        assert not (loss_strongest and loss_multimodal)
         self.flat, self.layout = flatten_parameters(model)
         self.grad = torch.zeros_like(self.flat)
         self.exp_avg = torch.zeros_like(self.flat)
@@ -247,6 +378,8 @@ class TrainStep:
                                                                               or bool(force_distributed))
         self.group = process_group
         self.world = dist.get_world_size(process_group) if self.distributed else 1
+        self.loss = StepLoss(self.variant, loss_multimodal, loss_padding, loss_strongest, model, self.distributed,
+                             process_group, self.world)
         self.buckets = GradBuckets(self.layout, process_group, self._agreed_bucket_count()) if self.distributed else None
         self._grads = {name: self.grad[o:o + n].view_as(dict(model.named_parameters())[name])
                        for name, o, n in self.layout}
@@ -334,8 +467,7 @@ class TrainStep:
         else:
             model.train()
         lr = self.current_lr(iteration)
-        if self.strongest:
-            gt = self.strongest_gt(gt).contiguous()
+        gt = self.loss.step_target(gt)
         mask = self._mask(mask)
         den = self._den_begin(mask)
         self.grad.zero_()
@@ -367,24 +499,13 @@ class TrainStep:
         """The reference's nn.DataParallel step (train/cli.py:159,243-258) over the chunks of this rank's batch, one after the
         other: every chunk is a replica with its own BatchNorm batch statistics, the loss is the masked mean over the WHOLE batch
         (every chunk is normalised by the whole batch's valid-pixel count and, for the multimodal UPR / padded UPR losses, by the
-        whole batch's sums -- all formed once, here, ahead of chunk 0), the gradients are summed in self.grad, and the BatchNorm
-        buffers move by chunk 0's forward pass only (device 0's buffers persist).  Under data parallelism the counts are the
+        whole batch's sums -- all formed once by StepLoss.chunks, ahead of chunk 0), the gradients are summed in self.grad, and the
+        BatchNorm buffers move by chunk 0's forward pass only (device 0's buffers persist).  Under data parallelism the counts are the
         global ones (`den` is _den_begin's pending all-reduce, which chunk 0 waits for behind its forward pass) and the bucket
         hooks belong to the last chunk's backward: nothing is all-reduced before every chunk has accumulated.
         fwd_bwd: _native_fwd_bwd or _torch_fwd_bwd; gt, mask: the whole batch's.  Returns the sum of the chunks' losses, which
         is this rank's whole-batch loss."""
-        if den is None:
-            den = mask.sum().double().reshape(1)
-        aux, mp = None, None
-        if self.variant == 'upr' and self.multimodal:
-            alpha = gt[:, :, 3]
-            if self.loss_padding is not None:             # (_padded_mpi's alpha, without a copy of the other planes)
-                alpha = alpha * (torch.abs(gt[:, :, 4]) < self.loss_padding).float()
-            aux = self._aux_sums(loss_mod.KIND_MULTI_UPR, alpha.sum(1), None)
-        elif self.variant == 'upr' and self.loss_padding is not None:
-            whole = (torch.abs(gt) < self.loss_padding).int()
-            aux, mp = self._aux_sums(loss_mod.KIND_UPR_PADDED, None, whole), whole.chunk(self.micro_batches)
-        share = _Chunks(len(chunks), den, aux, mask.numel() * self.world, mp)
+        share = self.loss.chunks(len(chunks), self.micro_batches, gt, mask, den)
         losses, saved = [], None
         buffers = list(self.model.buffers()) if fwd_bwd == self._torch_fwd_bwd and self.model.training else []
         for k, chunk in enumerate(chunks):
@@ -409,112 +530,11 @@ class TrainStep:
             den = self._den_end(den)
             if share is not None:
                 share.den, share.packs = den, tape.packs
-            if self.multimodal:
-                loss, gout = self._multimodal_loss(out, gt, mask, den, share)
-            else:
-                kind = KINDS[self.variant]
-                grid, half = None, 0.0
-                if kind == loss_mod.KIND_CE:
-                    grid = model._grid('torch', out.device)
-                    half = (model.disp_max - model.disp_min) / model.steps / 2.0
-                pad = self.loss_padding
-                if pad is not None and kind == loss_mod.KIND_UPR:     # train/cli.py:221-222: only the UPR loss takes it
-                    if share is None:
-                        mp = (torch.abs(gt) < pad).int()
-                        aux = self._scaled_aux(self._aux_override(loss_mod.KIND_UPR_PADDED, gt, mp))
-                    else:
-                        mp, aux = share.mp[share.index], share.chunk_aux(mask.numel())
-                    loss, gout = loss_mod.native_multi_loss(loss_mod.KIND_UPR_PADDED, out, gt, mask, mp, None, 0.0,
-                                                            True, den, aux)
-                else:
-                    loss, gout = loss_mod.native_loss(kind, out, gt, mask, grid, half, True, den)
+            loss, gout = self.loss.native(out, gt, mask, den, share)
             hooked = self.distributed and (share is None or share.last())
             on_done = (lambda key: self.buckets.ready(self.grad, key)) if hooked else None
             model._trunk.backward(p, tape, gout, self._trainable_grads or None, on_done)
         return loss
-
-    def _padded_mpi(self, mpi):
-        """--train_loss_padding with --train_loss_multimodal: planes outside the range lose their alpha
-        (train/cli.py:219-220).  The DPP target is built from the UNPADDED planes (:201-204 run before :219)."""
-        if self.loss_padding is None or self.variant == 'dpp':
-            return mpi
-        mpi = mpi.clone()
-        mpi[:, :, 3] *= (torch.abs(mpi[:, :, 4]) < self.loss_padding).float()
-        return mpi
-
-    def _multimodal_heads_loss(self, heads, mpi, mask, share=None):
-        model = self.model
-        mpi = self._padded_mpi(mpi)
-        if self.variant == 'upr' and share is not None:
-            return self._whole_batch_upr_loss(loss_mod.KIND_MULTI_UPR, heads, mpi, mask, None, share)
-        if self.variant == 'upr':
-            return loss_mod.ImprovedMultiUncertaintyL1Loss()(heads, mpi, mask)
-        if self.variant == 'dpp':
-            tgt = dl.mpi_to_weights(mpi, model.disp_min, model.disp_max, model.steps)
-            return loss_mod.MaskedCrossEntropy()(heads, tgt, mask)
-        return loss_mod.MultiMaskedL1Loss()(heads, mpi, mask)
-
-    def _aux_override(self, kind, target, mask_padding):
-        """whole-batch sums the multimodal UPR / padded UPR losses normalise by, summed over the ranks (the
-        reference evaluates the loss on the gathered batch, train/cli.py:245-255)"""
-        if not self.distributed:
-            return None
-        return self._aux_sums(kind, target[:, :, 3].sum(1) if kind == loss_mod.KIND_MULTI_UPR else None, mask_padding)
-
-    def _aux_sums(self, kind, tot, mask_padding):
-        """the two sums themselves, over this rank's tensors and then over the ranks.  tot: the total alpha per pixel (the
-        multimodal UPR loss: its sum and the count of pixels without a surface); mask_padding: the padded UPR loss's in-range
-        mask (its count)"""
-        if kind == loss_mod.KIND_MULTI_UPR:
-            aux = torch.stack([tot.sum().double(), (tot < 0.01).sum().double()])
-        else:
-            aux = torch.stack([mask_padding.sum().double(), torch.zeros((), dtype=torch.float64, device=mask_padding.device)])
-        if self.distributed:
-            dist.all_reduce(aux, group=self.group)
-        return aux
-
-    def _whole_batch_upr_loss(self, kind, heads, target, mask, mask_padding, share):
-        """The multimodal UPR / padded UPR loss of a chunk on the stock path, with the whole batch's normalisers where the loss
-        modules form a tensor's own (loss.py:336-372, 264-294): the masked mean over the chunk of
-        ((exp(-logvar) |mean - d_p| + logvar) alpha_p summed over the planes / mean total alpha - logvar * oor * pixels / #oor) / 2,
-        resp. ((exp(-logvar) |mean - gt| + logvar) * in * pixels / #in - logvar * (1 - in) * pixels / #(1 - in)) / 2
-        (a factor whose count is 0 is 1).  On the GPU the fused kernel with its aux_override, as the native path calls it."""
-        mean, logvar = heads['mean'], heads['logvar']
-        if mean.is_cuda:
-            return loss_mod._NativeMultiLossFn.apply(kind, target, mask, mask_padding, share.chunk_aux(mask.numel()),
-                                                     mean, logvar)
-        s0, s1, n = share.aux[0], share.aux[1], float(share.pixels)
-        if kind == loss_mod.KIND_MULTI_UPR:
-            weights, targets = target[:, :, 3], target[:, :, 4]
-            loss = torch.exp(-logvar).unsqueeze(1) * torch.abs(mean.unsqueeze(1) - targets) + logvar.unsqueeze(1)
-            loss = (loss * weights).sum(1) / (s0 / n).float()
-            oor = (weights.sum(1) < 0.01).float()
-            loss_oor = -logvar * oor * (n / s1).float()          # 0 * inf = NaN when no pixel lacks a surface, as in the reference
-        else:
-            mp = mask_padding.float()
-            one = torch.ones_like(s0)
-            loss = (torch.exp(-logvar) * torch.abs(mean - target) + logvar) * mp * torch.where(s0 > 0, n / s0, one).float()
-            loss_oor = -logvar * (1.0 - mp) * torch.where(n - s0 > 0, n / (n - s0), one).float()
-        return loss_mod._masked_mean((loss + loss_oor) / 2.0, mask)
-
-    def _multimodal_loss(self, out, mpi, mask, den, share=None):
-        """multimodal losses over (B,P,5,H,W) targets: fused HIP value + gradient (mmlf_loss_multi_fwd_bwd)"""
-        model = self.model
-        mpi = self._padded_mpi(mpi)
-        kind = {'base': loss_mod.KIND_MULTI_L1, 'upr': loss_mod.KIND_MULTI_UPR, 'dpp': loss_mod.KIND_MULTI_CE}[self.variant]
-        grid, half = None, 0.0
-        if kind == loss_mod.KIND_MULTI_CE:
-            grid = model._grid('torch', out.device)
-            half = (model.disp_max - model.disp_min) / model.steps / 2.0
-        if share is not None:                   # a chunk of a step: the whole batch's sums, scaled to the chunk's pixels
-            aux = share.chunk_aux(mask.numel()) if kind == loss_mod.KIND_MULTI_UPR else None
-        else:
-            aux = self._scaled_aux(self._aux_override(kind, mpi, None) if kind == loss_mod.KIND_MULTI_UPR else None)
-        return loss_mod.native_multi_loss(kind, out, mpi, mask, None, grid, half, True, den, aux)
-
-    def _scaled_aux(self, aux):
-        # the kernel forms mean = aux[0] / n_local and n_local / aux[1]: pass the global sums divided by the world size
-        return None if aux is None else aux / self.world
 
     def _torch_fwd_bwd(self, h, v, i_, d, gt, mask, den, share=None):
         """share: this pass is a chunk of a step (_Chunks), None: the whole step.  `.grad` accumulates over the chunks and goes
@@ -527,21 +547,7 @@ class TrainStep:
         den = self._den_end(den)
         if share is not None:
             share.den = den
-        if self.multimodal:
-            loss = self._multimodal_heads_loss(out, gt, mask, share)
-        elif self.variant == 'upr' and share is not None and self.loss_padding is not None:
-            loss = self._whole_batch_upr_loss(loss_mod.KIND_UPR_PADDED, out, gt, mask, share.mp[share.index], share)
-        elif self.variant == 'upr':
-            mp = None if self.loss_padding is None else (torch.abs(gt) < self.loss_padding).int()
-            loss = loss_mod.ImprovedUncertaintyL1Loss()(out, gt, mask, mp)
-        elif self.variant == 'dpp':
-            tgt = dl.reg_to_class(gt, model.disp_min, model.disp_max, model.steps)
-            loss = loss_mod.MaskedCrossEntropy()(out, tgt, mask)
-        else:
-            loss = loss_mod.MaskedL1Loss()(out, gt, mask)
-        if den is not None:     # global masked mean: rescale the local mean to the shared denominator
-            cnt = mask.sum().double()
-            loss = loss * (cnt / den.squeeze()).float() if cnt > 0 else loss
+        loss = self.loss.torch(out, gt, mask, den, share)
         loss.backward()
         if share is not None and not share.last():
             return loss.detach()

@@ -99,7 +99,8 @@ def test_step_equals_the_chunk_by_chunk_emulation(B, n, variant):
     assert float(solid.float().mean()) > (0.5 if variant == 'dpp' else 0.9)       # (tests/test_microbatch_cpu.py's floors)
 
 
-LOSS_KW = {'upr': {}, 'multi_upr': {'loss_multimodal': True}}
+LOSS_KW = {'upr': {}, 'multi_upr': {'loss_multimodal': True}, 'upr_padded': {'loss_padding': 1.5},
+           'multi_upr_padded': {'loss_multimodal': True, 'loss_padding': 1.5}}
 
 
 @pytest.mark.parametrize('net', ['eval_mode', 'no_batchnorm'])
@@ -107,12 +108,14 @@ LOSS_KW = {'upr': {}, 'multi_upr': {'loss_multimodal': True}}
 def test_chunks_change_nothing_where_batchnorm_cannot_differ(name, net):
     """n = 3 on B = 5 (chunks of 2, 2 and 1 samples) against n = 1: the loss to rtol 1e-5, every gradient tensor within
     test_microbatch_cpu.chunk_invariance_bound.  The kernels add to that bound's reasons a power-of-two operand scale taken from
-    the tensor's largest magnitude (the chunk's, not the batch's), which moves the f16 split's rounding at the 2^-22 level."""
+    the tensor's largest magnitude (the chunk's, not the batch's), which moves the f16 split's rounding at the 2^-22 level.
+    The padded forms (+-1.5: every sample of either target has values on both sides) take the per-chunk in-range masks and the
+    whole batch's sums through the chunks."""
     kw, B, n = LOSS_KW[name], 5, 3
     stacks, gt, mask = (torch.from_numpy(np.asarray(x)) for x in synth.synth_inputs(B, PS, seed=6))
     mask[0, :, :9] = 0
     mask[3] = 0
-    target = _mpi(B) if kw else gt          # (pixels without a surface in sample 0 alone: the other chunks' own count is 0)
+    target = _mpi(B) if kw.get('loss_multimodal') else gt          # (pixels without a surface in sample 0 alone: the other chunks' own count is 0)
     stacks, target, mask = _cuda(*stacks), *_cuda(target, mask)
     model_kw, step_kw = ({'model_no_batchnorm': True}, {}) if net == 'no_batchnorm' else ({}, {'train_eval_mode': True})
 
@@ -122,10 +125,12 @@ def test_chunks_change_nothing_where_batchnorm_cannot_differ(name, net):
     loss1, one = run(1)
     loss, step = run(n)
     assert np.isfinite(loss1) and float(one.grad.abs().max()) > 0
+    print(f'{name}, {net}: loss {loss!r} in {n} chunks, {loss1!r} in one')
     np.testing.assert_allclose(loss, loss1, rtol=1e-5)
     for pname, o, cnt in step.layout:
         g, g1 = step.grad[o:o + cnt], one.grad[o:o + cnt]
         worst, tol = float((g - g1).abs().max()), chunk_invariance_bound(g1, n)
+        print(f'  {pname}: worst {worst:.3e}, bound {tol:.3e}')
         assert worst <= tol, (pname, worst, tol)
 
 

@@ -97,6 +97,31 @@ def test_train_step_multimodal_with_padding(dev, variant):
         assert float((got - ref).norm()) <= 2e-3 * float(ref.norm()) + 1e-6, n
 
 
+@pytest.mark.gpu
+def test_train_step_padded_upr():
+    """TrainStep(loss_padding=...) on the UPR net without --train_loss_multimodal (train/cli.py:221-222): one native step
+    through mmlf_loss_multi_fwd_bwd(kind 6) equals ImprovedUncertaintyL1Loss with mask_padding = |gt| < padding through plain
+    autograd on the CPU module path.  Every sample of this gt has pixels on both sides of +-1.5."""
+    kw = dict(TINY_KW, model_uncert=True)
+    state = synth.synth_state(synth.param_spec(**kw), 9)
+    stacks, gt, mask = (torch.from_numpy(np.asarray(x)) for x in synth.synth_inputs(5, 16, seed=6))
+    in_range = (torch.abs(gt) < 1.5).int()
+    assert all(0 < int(s.sum()) < s.numel() for s in in_range)
+    st = TrainStep(_fresh(kw, state, 'cuda'), lr=1e-3, loss_margin=3, loss_padding=1.5)
+    assert st.model._native_ok
+    l1 = st(*[s.cuda() for s in stacks], gt.cuda(), mask.cuda(), 1)
+    m2 = _fresh(kw, state, 'cpu')
+    m2.train()
+    l2 = loss.ImprovedUncertaintyL1Loss()(m2(*stacks), gt, st._mask(mask.cuda()).cpu(), in_range)
+    print(f'padded UPR step: loss {float(l1)!r} against {float(l2.detach())!r}')
+    np.testing.assert_allclose(float(l1), float(l2.detach()), rtol=2e-5)
+    l2.backward()
+    for (n, o, cnt), (_, p) in zip(st.layout, m2.named_parameters()):
+        ref, got = p.grad.reshape(-1), st.grad[o:o + cnt].cpu()
+        print(f'  {n}: |got - ref| {float((got - ref).norm()):.3e}, |ref| {float(ref.norm()):.3e}')
+        assert float((got - ref).norm()) <= 2e-3 * float(ref.norm()) + 1e-6, n
+
+
 @pytest.mark.parametrize('dev', DEVICES)
 def test_train_eval_mode_vs_reference(dev):
     """--train_eval_mode (reference train/cli.py:227-230): the optimisation step runs with model.eval(), i.e.
