@@ -191,6 +191,50 @@ def call_eval(name, *args):
         raise RuntimeError(f'{name} failed: {lib.mmlf_eval_last_error().decode()}')
 
 
+# ---- libmmlf_ese_hip.so: the Ensamble's backward kernels (include/mmlf_ese_hip.h), an ABI of their own ----
+ESE_LIB_PATH = os.path.join(_HERE, 'csrc', 'libmmlf_ese_hip.so')
+_ESE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'mmlf_ese_hip.h')
+
+
+def _ese_header_text():
+    with open(_ESE_HEADER) as f:
+        return f.read()
+
+
+ESE_SIGNATURES = signatures_from_header(_ese_header_text())
+ESE_ABI_VERSION = int(re.search(r'^#define\s+MMLF_ESE_ABI_VERSION\s+(\d+)', _ese_header_text(), re.M).group(1))
+ESE_MAX_TAB = int(re.search(r'^#define\s+MMLF_ESE_MAX_TAB\s+(\d+)', _ese_header_text(), re.M).group(1))
+_ese_lib = None
+
+
+def load_ese():
+    """Load libmmlf_ese_hip.so once; raise if it is absent or of another ABI version (no fallback).  torch is imported at
+    this module's top, ahead of the library, for the reason load() gives."""
+    global _ese_lib
+    if _ese_lib is None:
+        if not os.path.exists(ESE_LIB_PATH):
+            raise RuntimeError(f'{ESE_LIB_PATH} not found: build it with `python -m mmlf_amd.csrc.build` '
+                               '(the Ensamble\'s backward has no fallback on CUDA tensors)')
+        lib = ctypes.CDLL(ESE_LIB_PATH)
+        got = lib.mmlf_ese_abi_version() if hasattr(lib, 'mmlf_ese_abi_version') else None
+        if got != ESE_ABI_VERSION:
+            raise RuntimeError(f'{ESE_LIB_PATH} implements ABI version {got}, this package needs {ESE_ABI_VERSION}: '
+                               'rebuild it with `python -m mmlf_amd.csrc.build --force`')
+        for name, (res, args) in ESE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _ese_lib = lib
+    return _ese_lib
+
+
+def call_ese(name, *args):
+    """Invoke an int-returning entry point of the Ensamble-backward library; nonzero status -> RuntimeError."""
+    lib = load_ese()
+    if getattr(lib, name)(*args) != 0:
+        raise RuntimeError(f'{name} failed: {lib.mmlf_ese_last_error().decode()}')
+
+
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

@@ -99,6 +99,33 @@ def build_eval(force=False, verbose=True):
     return EVAL_LIB
 
 
+# The Ensamble's backward kernels (include/mmlf_ese_hip.h): a third library on the same terms -- none of its files is in
+# SOURCES, HASHED or EVAL_SOURCES.
+ESE_SOURCES = ['ensamble_grad.hip']
+ESE_LIB = os.path.join(HERE, 'libmmlf_ese_hip.so')
+ESE_HEADER = os.path.join(HERE, '..', '..', 'include', 'mmlf_ese_hip.h')
+
+
+def ese_stale():
+    if not os.path.exists(ESE_LIB):
+        return True
+    t = os.path.getmtime(ESE_LIB)
+    deps = [os.path.join(HERE, s) for s in ESE_SOURCES] + [os.path.join(HERE, 'build.py'), ESE_HEADER]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_ese(force=False, verbose=True):
+    """libmmlf_ese_hip.so, with the FLAGS of the training library (-ffp-contract=off: its float32 sums are written
+    operation by operation)"""
+    if not force and not ese_stale():
+        return ESE_LIB
+    cmd = [HIPCC, *FLAGS, '-shared', *[os.path.join(HERE, s) for s in ESE_SOURCES], '-o', ESE_LIB]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return ESE_LIB
+
+
 if __name__ == '__main__':
     if '--source-hash' in sys.argv:
         print(source_hash())
@@ -107,3 +134,4 @@ if __name__ == '__main__':
     else:
         build(force='--force' in sys.argv)
         build_eval(force='--force' in sys.argv)
+        build_ese(force='--force' in sys.argv)

@@ -1046,7 +1046,7 @@ class Trunk:
             side.kept = None                         # (no launch of this block's: the last launch's tensors go, see launch())
         return dx
 
-    def backward(self, p, tape, grad_output, grads, on_done=None, input_grads=None):
+    def backward(self, p, tape, grad_output, grads, on_done=None, input_grads=None, packed_grads=False):
         """grad_output: (B,oc,H,W) NCHW.  grads: dict name -> tensor, ACCUMULATED into
         (the caller zeroes them), or None: no parameter gradient is formed (no weight-gradient launch at all; required
         for a tape of forward(frozen=True)).  The dict holds the names the forward pass was given as trainable= (all of
@@ -1057,7 +1057,10 @@ class Trunk:
         input_grads: four bools (streams H, V, I, D), the view stacks whose gradient is wanted; default none.  Returns a list
         of four entries: the (B, views, 3, H, W) float32 gradient of a wanted stack, None for the others.  The parameter
         gradients do not depend on it: the same weight-gradient launches in the same order.  The tape is used up: a block's
-        record is released as soon as its launches are enqueued, the concat buffer at the end."""
+        record is released as soon as its launches are enqueued, the concat buffer at the end.
+        packed_grads (the mirror of forward's packed=): a wanted stack's entry is (grid tensor, cs) instead -- the data
+        gradient of the stream's first convolution as the kernel wrote it, extent (H, W) at (1, 1), 3 views channels of
+        channel stride cs -- and no mmlf_unpack_nchw runs (the Ensamble's mmlf_ese_unshift_sum reads that layout)."""
         geo, dev = tape.geo, tape.device
         check(grad_output, 'grad_output', dev, shape=(geo.B, self.oc, geo.H, geo.W), contiguous=False)
         fplan = tape.plan
@@ -1104,7 +1107,10 @@ class Trunk:
             if bp is not None:               # (live blocks sit on top of a chain: nothing beneath a block without a plan runs)
                 gs = self._block_bwd(tape, rec, bp, grads, gs)
             if site.k == 0:
-                if want[s]:
+                if want[s] and packed_grads:
+                    assert gs.off == 0
+                    dstacks[s] = (gs.t, gs.cs)
+                elif want[s]:
                     # gs: the gradient of the stream's packed input, extent (H, W) at (1, 1), 3 views channels of gs.cs
                     dstacks[s] = torch.empty((B, self.views, 3, H, W), dtype=torch.float32, device=dev)
                     call('mmlf_unpack_nchw', ptr(gs.t), gs.cs, ptr(dstacks[s]), 3 * self.views, B, H, W, _lib.stream_ptr())
