@@ -235,6 +235,51 @@ def call_ese(name, *args):
         raise RuntimeError(f'{name} failed: {lib.mmlf_ese_last_error().decode()}')
 
 
+# ---- libmmlf_data_hip.so: the composable patch chain's kernels (include/mmlf_data_hip.h), an ABI of their own ----
+DATA_LIB_PATH = os.path.join(_HERE, 'csrc', 'libmmlf_data_hip.so')
+_DATA_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'mmlf_data_hip.h')
+
+
+def _data_header_text():
+    with open(_DATA_HEADER) as f:
+        return f.read()
+
+
+DATA_SIGNATURES = signatures_from_header(_data_header_text())
+DATA_ABI_VERSION = int(re.search(r'^#define\s+MMLF_DATA_ABI_VERSION\s+(\d+)', _data_header_text(), re.M).group(1))
+DATA_FLAGS = {name: int(value) for name, value in
+              re.findall(r'^#define\s+MMLF_DATA_(SHEAR|COLOR|BRIGHT|ROLL|GT_MUL|GT_DIV)\s+(\d+)', _data_header_text(), re.M)}
+_data_lib = None
+
+
+def load_data():
+    """Load libmmlf_data_hip.so once; raise if it is absent or of another ABI version (no fallback).  torch is imported at
+    this module's top, ahead of the library, for the reason load() gives."""
+    global _data_lib
+    if _data_lib is None:
+        if not os.path.exists(DATA_LIB_PATH):
+            raise RuntimeError(f'{DATA_LIB_PATH} not found: build it with `python -m mmlf_amd.csrc.build` '
+                               '(PatchPipeline(chain=...) has no fallback)')
+        lib = ctypes.CDLL(DATA_LIB_PATH)
+        got = lib.mmlf_data_abi_version() if hasattr(lib, 'mmlf_data_abi_version') else None
+        if got != DATA_ABI_VERSION:
+            raise RuntimeError(f'{DATA_LIB_PATH} implements ABI version {got}, this package needs {DATA_ABI_VERSION}: '
+                               'rebuild it with `python -m mmlf_amd.csrc.build --force`')
+        for name, (res, args) in DATA_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _data_lib = lib
+    return _data_lib
+
+
+def call_data(name, *args):
+    """Invoke an int-returning entry point of the patch-chain library; nonzero status -> RuntimeError."""
+    lib = load_data()
+    if getattr(lib, name)(*args) != 0:
+        raise RuntimeError(f'{name} failed: {lib.mmlf_data_last_error().decode()}')
+
+
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

@@ -126,6 +126,33 @@ def build_ese(force=False, verbose=True):
     return ESE_LIB
 
 
+# The composable patch chain (include/mmlf_data_hip.h): a fourth library on the same terms -- none of its files is in
+# SOURCES, HASHED, EVAL_SOURCES or ESE_SOURCES.
+DATA_SOURCES = ['patch_chain.hip']
+DATA_LIB = os.path.join(HERE, 'libmmlf_data_hip.so')
+DATA_HEADER = os.path.join(HERE, '..', '..', 'include', 'mmlf_data_hip.h')
+
+
+def data_stale():
+    if not os.path.exists(DATA_LIB):
+        return True
+    t = os.path.getmtime(DATA_LIB)
+    deps = [os.path.join(HERE, s) for s in DATA_SOURCES] + [os.path.join(HERE, 'build.py'), DATA_HEADER]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_data(force=False, verbose=True):
+    """libmmlf_data_hip.so, with the FLAGS of the training library (-ffp-contract=off: the gather restates
+    mmlf_patch_gather's float32 arithmetic operation by operation)"""
+    if not force and not data_stale():
+        return DATA_LIB
+    cmd = [HIPCC, *FLAGS, '-shared', *[os.path.join(HERE, s) for s in DATA_SOURCES], '-o', DATA_LIB]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return DATA_LIB
+
+
 if __name__ == '__main__':
     if '--source-hash' in sys.argv:
         print(source_hash())
@@ -135,3 +162,4 @@ if __name__ == '__main__':
         build(force='--force' in sys.argv)
         build_eval(force='--force' in sys.argv)
         build_ese(force='--force' in sys.argv)
+        build_data(force='--force' in sys.argv)
