@@ -280,6 +280,50 @@ def call_data(name, *args):
         raise RuntimeError(f'{name} failed: {lib.mmlf_data_last_error().decode()}')
 
 
+# ---- libmmlf_scene_hip.so: the scene builder's kernels (include/mmlf_scene_hip.h), an ABI of their own ----
+SCENE_LIB_PATH = os.path.join(_HERE, 'csrc', 'libmmlf_scene_hip.so')
+_SCENE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'mmlf_scene_hip.h')
+
+
+def _scene_header_text():
+    with open(_SCENE_HEADER) as f:
+        return f.read()
+
+
+SCENE_SIGNATURES = signatures_from_header(_scene_header_text())
+SCENE_ABI_VERSION = int(re.search(r'^#define\s+MMLF_SCENE_ABI_VERSION\s+(\d+)', _scene_header_text(), re.M).group(1))
+SCENE_MAX_WSIZE = int(re.search(r'^#define\s+MMLF_SCENE_MAX_WSIZE\s+(\d+)', _scene_header_text(), re.M).group(1))
+_scene_lib = None
+
+
+def load_scene_lib():
+    """Load libmmlf_scene_hip.so once; raise if it is absent or of another ABI version (no fallback).  torch is imported
+    at this module's top, ahead of the library, for the reason load() gives."""
+    global _scene_lib
+    if _scene_lib is None:
+        if not os.path.exists(SCENE_LIB_PATH):
+            raise RuntimeError(f'{SCENE_LIB_PATH} not found: build it with `python -m mmlf_amd.csrc.build` '
+                               '(mmlf_amd.scenes has no fallback on CUDA tensors)')
+        lib = ctypes.CDLL(SCENE_LIB_PATH)
+        got = lib.mmlf_scene_abi_version() if hasattr(lib, 'mmlf_scene_abi_version') else None
+        if got != SCENE_ABI_VERSION:
+            raise RuntimeError(f'{SCENE_LIB_PATH} implements ABI version {got}, this package needs {SCENE_ABI_VERSION}: '
+                               'rebuild it with `python -m mmlf_amd.csrc.build --force`')
+        for name, (res, args) in SCENE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _scene_lib = lib
+    return _scene_lib
+
+
+def call_scene(name, *args):
+    """Invoke an int-returning entry point of the scene library; nonzero status -> RuntimeError."""
+    lib = load_scene_lib()
+    if getattr(lib, name)(*args) != 0:
+        raise RuntimeError(f'{name} failed: {lib.mmlf_scene_last_error().decode()}')
+
+
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

@@ -153,6 +153,33 @@ def build_data(force=False, verbose=True):
     return DATA_LIB
 
 
+# The scene builder (include/mmlf_scene_hip.h): a fifth library on the same terms -- none of its files is in SOURCES, HASHED,
+# EVAL_SOURCES, ESE_SOURCES or DATA_SOURCES.
+SCENE_SOURCES = ['scene.hip']
+SCENE_LIB = os.path.join(HERE, 'libmmlf_scene_hip.so')
+SCENE_HEADER = os.path.join(HERE, '..', '..', 'include', 'mmlf_scene_hip.h')
+
+
+def scene_stale():
+    if not os.path.exists(SCENE_LIB):
+        return True
+    t = os.path.getmtime(SCENE_LIB)
+    deps = [os.path.join(HERE, s) for s in SCENE_SOURCES] + [os.path.join(HERE, 'build.py'), SCENE_HEADER]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_scene(force=False, verbose=True):
+    """libmmlf_scene_hip.so, with the FLAGS of the training library (-ffp-contract=off: the texture mask's float32 sum and
+    its one division are written operation by operation)"""
+    if not force and not scene_stale():
+        return SCENE_LIB
+    cmd = [HIPCC, *FLAGS, '-shared', *[os.path.join(HERE, s) for s in SCENE_SOURCES], '-o', SCENE_LIB]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return SCENE_LIB
+
+
 if __name__ == '__main__':
     if '--source-hash' in sys.argv:
         print(source_hash())
@@ -163,3 +190,4 @@ if __name__ == '__main__':
         build_eval(force='--force' in sys.argv)
         build_ese(force='--force' in sys.argv)
         build_data(force='--force' in sys.argv)
+        build_scene(force='--force' in sys.argv)

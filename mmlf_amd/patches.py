@@ -240,7 +240,8 @@ class PatchPipeline:
     """Scenes cached on the GPU + the fused transform chain.
 
     scenes: list of tuples (h, v, i, d, center, gt, mpi, mask, index) as ``HCI4D.load_scene`` returns
-    them (hci4d.py:150-254), all of one frame size.  ``train_shift`` is the CLI's fixed pre-shift
+    them (hci4d.py:150-254), all of one frame size: numpy arrays, or torch tensors on the CPU or already on ``device``
+    (``mmlf_amd.scenes.assemble_scene``; a device tensor makes no host round trip).  ``train_shift`` is the CLI's fixed pre-shift
     (train/cli.py:93-94), applied once to the cached scenes.
 
     ``chain``: None runs the CLI's chain with its three knobs (``max_downscale``, ``augment``, ``train_shift``).  A list
@@ -262,14 +263,25 @@ class PatchPipeline:
         self._maps = {}
         self.ps, self.max_downscale, self.augment = int(ps), int(max_downscale), bool(augment)
         dev = torch.device(device)
-        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
+
+        def f32(a):          # a tensor (mmlf_amd.scenes.assemble_scene; CPU or already on `dev`) is taken as it is
+            if isinstance(a, torch.Tensor):
+                return a.detach().to(device=dev, dtype=torch.float32)
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+
+        def i32(a):
+            if isinstance(a, torch.Tensor):
+                return a.detach().to(device=dev, dtype=torch.int32)
+            return torch.from_numpy(np.ascontiguousarray(a).astype(np.int32)).to(dev)
+
+        def host(a):
+            return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
         self.stacks = torch.stack([torch.stack([f32(s[k]) for k in range(4)]) for s in scenes])  # (S,4,V,3,H,W)
         self.center = torch.stack([f32(s[4]) for s in scenes])
         self.gt = torch.stack([f32(s[5]) for s in scenes])
         self.mpi = torch.stack([f32(s[6]) for s in scenes])
-        self.mask = torch.stack([torch.from_numpy(np.ascontiguousarray(s[7]).astype(np.int32)).to(dev)
-                                 for s in scenes])
-        self.index = [np.atleast_1d(s[8]) for s in scenes]
+        self.mask = torch.stack([i32(s[7]) for s in scenes])
+        self.index = [np.atleast_1d(host(s[8])) for s in scenes]
         self.S, _, self.V, _, self.Hf, self.Wf = self.stacks.shape
         self.P = self.mpi.shape[1]
         self.rot_src = torch.from_numpy(rotation_sources(self.V)).to(dev)
